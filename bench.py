@@ -15,8 +15,12 @@ fp32-GEMM error bound and the 1e-5 loss bar by tests/; --precision split3 is the
 processes spawned here before anything touches a GPU; one rank per GPU) the 50 tasks are sharded contiguously over the ranks and the trunk gradients
 are all-reduced over RCCL; the problem size is fixed, so scaling is "strong".
 
-Prints ONE JSON line on rank 0 (keys per the driver contract, plus roofline and
-cpu_baseline).
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0 (keys per
+the driver contract).  --full adds, after the timed steps, what takes runs of its own: the per-kernel
+event pass and serialised step behind `roofline` / `gemm_families`, and the PyTorch-CPU
+`cpu_baseline`.  --dump-outputs DIR starts the timed steps from the state the set-up left
+(parameters, optimizer, index and noise streams: the same from run to run, however many warm-up
+and settle steps ran) and writes what they computed as DIR/<name>.npy.
 """
 
 from __future__ import annotations
@@ -197,6 +201,40 @@ def cpu_baseline(T, W, clip, steps, c0_steps):
     return out
 
 
+DUMP_MAX_ELEMS = 2_000_000  # per array: 8 MB of float32, so every array of a run together stays far under 64 MB
+
+
+def dump_outputs(path, arrays, rank):
+    """--dump-outputs: each array flat as <path>/<name>.npy (float64 stays, anything else as float32;
+    ranks above 0 write <name>.rank<r>.npy); an array of more than DUMP_MAX_ELEMS elements as a fixed
+    sample of them, at sorted indices drawn without replacement from default_rng(0)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32).reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + ("" if rank == 0 else f".rank{rank}") + ".npy"), a)
+
+
+def sac_state(eng):
+    """Everything a step reads and writes besides the (static) buffer: the ten parameter / Adam
+    tensors, the Adam counts, the action-noise counter and the index stream."""
+    return ({w: eng.get_params(w) for w in range(10)}, [eng.get_adam_count(i) for i in range(3)],
+            eng.noise_state(), eng.get_rng_state())
+
+
+def sac_restore(eng, state):
+    tensors, counts, noise, rng = state
+    for w, v in tensors.items():
+        eng.set_params(w, v)
+    for i, c in enumerate(counts):
+        eng.set_adam_count(i, c)
+    eng.set_noise_state(*noise)
+    eng.set_rng_state(rng)
+    eng.synchronize()
+
+
 def bench_drq(args, world, rank, local_rank, dist):
     """configs[4]: one DrQ-eps training step = sample_unbalanced(256) from a full device Atari
     buffer (host Dirichlet / index draws included) + augmentation + the three ImpalaDQN passes,
@@ -224,6 +262,8 @@ def bench_drq(args, world, rank, local_rank, dist):
         o = np.roll(frames, i, axis=-1)
         e.buffer_add(o, np.roll(o, 1, axis=-1), rng.integers(0, 18, T), rng.standard_normal(T).astype(np.float32),
                      np.zeros(T, np.float32), (rng.random(T) < 0.01).astype(np.float32))
+    tensors = (L.DRQ_PARAMS, L.DRQ_TARGET, L.DRQ_ADAM_MU, L.DRQ_ADAM_NU)
+    start = ({w: e.get_params(w) for w in tensors}, e.get_step()) if args.dump_outputs else None
     e.sample_unbalanced_update(args.warmup)
     e.synchronize()
     settle = 0
@@ -237,7 +277,14 @@ def bench_drq(args, world, rank, local_rank, dist):
         settle = settle[0]
         e.sample_unbalanced_update(settle)
         e.synchronize()
-    e.set_timing(False)  # the timed steps run without events (as the SAC bench); then an events pass
+    e.set_timing(False)  # the timed steps run without events (as the SAC bench); --full: then an events pass
+    if start:  # the timed steps start from the set-up's state and streams
+        for w, v in start[0].items():
+            e.set_params(w, v)
+        e.set_step(start[1])
+        e.seed_rng(1 + rank)
+        e.seed_augment(2 + rank)
+        e.synchronize()
     if dist:
         dist.barrier()
     torch.cuda.synchronize(local_rank)
@@ -251,15 +298,11 @@ def bench_drq(args, world, rank, local_rank, dist):
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    e.set_timing(True)
-    e.sample_unbalanced_update(args.steps)
-    e.synchronize()
-    ms, nl, fl = e.timing()
-    e.set_timing(False)
     logs = e.logs()
-    e.close()
     assert all(math.isfinite(v) for v in logs.values()), logs
-    achieved = (fl / nl) / (ms / nl * 1e-3) / 1e12 if nl else 0.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logs": np.array([logs[k] for k in L.DRQ_LOG_KEYS], np.float64),
+                                         "params": e.get_params(L.DRQ_PARAMS), "target": e.get_params(L.DRQ_TARGET)}, rank)
     out = {
         "metric": DRQ_METRIC, "value": world * args.steps / elapsed, "unit": "DrQ gradient-steps/sec",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -270,6 +313,21 @@ def bench_drq(args, world, rank, local_rank, dist):
                                "task embedding 32, dense 512, 18 actions x 51 atoms, 3-step returns",
                    "global_batch": 256 * world, "batch_per_replica": 256, "sampler": "sample_unbalanced",
                    "parallelism": f"replicas{world}" if world > 1 else "single"},
+        "logs": logs,
+    }
+    if not args.full:
+        e.close()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
+    e.set_timing(True)
+    e.sample_unbalanced_update(args.steps)
+    e.synchronize()
+    ms, nl, fl = e.timing()
+    e.set_timing(False)
+    e.close()
+    achieved = (fl / nl) / (ms / nl * 1e-3) / 1e12 if nl else 0.0
+    out.update({
         "roofline": {"bound": "valu", "kernel": "conv_fwd_kernel<ci, co, *, *> (IMPALA 3x3 convs, direct fp32 FMA "
                                                 "on the vector ALUs; an MFMA implicit GEMM is not built, DESIGN 6b)",
                      "achieved": achieved, "peak": FP32_VALU_PEAK_TF, "peak_basis": "FP32 vector peak",
@@ -278,8 +336,7 @@ def bench_drq(args, world, rank, local_rank, dist):
                      "algorithmic_flops_per_launch": fl / max(nl, 1),
                      "timing": "HIP events per launch on the engine stream, every 8th update of a second pass of "
                                "the timed steps (the timed pass runs without events)"},
-        "logs": logs,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import drq as od  # the cpu_baseline leg only
 
@@ -337,6 +394,76 @@ def spawn_ranks(n):
     return bad[0] if bad else 0
 
 
+def gemm_report(eng, args, live):
+    """--full: the per-kernel figures of the result line, from runs of their own after the timed
+    steps: `roofline` of the dominant GEMM family, the GEMM time per step and every family's share."""
+    events_ms = None
+    if live:  # the events pass: the same steps again, every GEMM launch bracketed by HIP events
+        eng.set_timing(True)
+        a = time.perf_counter()
+        eng.update_many(args.steps)
+        eng.synchronize()
+        events_ms = 1e3 * (time.perf_counter() - a) / args.steps
+        eng.set_timing(False)
+
+    # dominant-kernel roofline from the per-launch HIP events
+    names = dict(GEMM_FAMILIES["split3" if args.precision == "bf16" else args.precision])
+    fam = {f: eng.timing(f) for f in names} if live else None
+    # the same kernels solo: one extra step serialised on one stream.  Eager: context for the
+    # fraction (under the step's concurrency a launch shares the CUs with its neighbours).
+    # Graph: the replays carry no events, so this IS the measurement (rocprof's mean over the
+    # replays agrees within a few %).
+    eng.set_timing(True, serial=True)
+    eng.update_many(1)
+    eng.synchronize()
+    solo = {f: eng.timing(f) for f in names}
+    eng.set_timing(False)
+    for f in names:  # the kernel the engine actually launched for each family
+        k = eng.timing_kernel(f)
+        if k and k != "gemm_x3p_kernel":
+            names[f] = k + " (" + names[f].split(" (", 1)[1]
+    if fam is None:
+        fam = solo
+    timed_steps = args.steps if live else 1
+    dom = max(fam, key=lambda f: fam[f][0])
+    ms, nl, fl = fam[dom]
+    gemm_ms = sum(v[0] for v in fam.values()) / timed_steps
+    gemm_fl = sum(v[2] for v in fam.values()) / timed_steps
+    achieved = (fl / nl) / (ms / nl * 1e-3) / 1e12 if nl else 0.0
+    traffic, traffic_src = pmc_traffic(args.precision, dom, args.workload)
+    if args.precision == "split3":  # 6 bf16 MFMA products per fp32 multiply-add
+        peak, basis = BF16_MFMA_PEAK_TF / 6.0, "bf16 dense MFMA peak / 6 products (fp32-accurate split)"
+    elif args.precision == "split2h":  # 3 fp16 MFMA products (fp16 runs at the bf16 rate)
+        peak, basis = BF16_MFMA_PEAK_TF / 3.0, "fp16 dense MFMA peak / 3 products (fp32-accurate 2xfp16 split)"
+    elif args.precision == "bf16":
+        peak, basis = BF16_MFMA_PEAK_TF, "bf16 dense MFMA peak"
+    else:
+        peak, basis = FP32_MFMA_PEAK_TF, "f32-input MFMA dense peak"
+    return {
+        "roofline": {"bound": "mfma", "kernel": names[dom], "achieved": achieved,
+                     "peak": peak, "peak_basis": basis, "unit": "TFLOP/s", "frac": achieved / peak,
+                     "traffic": traffic, "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, gfx950-corrected)",
+                     "traffic_source": traffic_src, "launches": nl, "avg_launch_us": 1e3 * ms / max(nl, 1),
+                     "algorithmic_flops_per_launch": fl / max(nl, 1),
+                     "timing": "HIP events per launch over a second pass of the timed eager steps (the "
+                               "timed pass runs without events)" if live
+                     else "graph replays carry no events: HIP events per launch in one serialised step",
+                     "events_pass_ms_per_step": events_ms,
+                     "clock": pmc_clock(args.precision, dom, args.workload),
+                     "solo": {"achieved": (solo[dom][2] / max(solo[dom][1], 1)) / (solo[dom][0] / max(solo[dom][1], 1) * 1e-3) / 1e12
+                              if solo[dom][0] else None,
+                              "avg_launch_us": 1e3 * solo[dom][0] / max(solo[dom][1], 1),
+                              "frac": ((solo[dom][2] / (solo[dom][0] * 1e-3) / 1e12) / peak) if solo[dom][0] else None,
+                              "timing": "one extra step with every kernel serialised on one stream"}},
+        "gemm_kernel_ms_per_step": gemm_ms,  # sum of GEMM launch durations (they overlap across streams)
+        "gemm_tflops_per_s": gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms else 0.0,
+        "gemm_families": {names[f]: {"ms_per_step": v[0] / timed_steps, "launches_per_step": v[1] / timed_steps,
+                                     "avg_launch_us": 1e3 * v[0] / max(v[1], 1),
+                                     "tflops": v[2] / (v[0] * 1e-3) / 1e12 if v[0] else 0.0}
+                          for f, v in fam.items()},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -358,7 +485,13 @@ def main():
                          "for a once-per-second utilisation sampler to see the GPU busy)")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-c0-steps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel event pass and the serialised step "
+                         "(roofline, gemm_families) and the PyTorch-CPU baseline; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="start the timed steps from the state the set-up left and write what they computed "
+                         "(logs and parameters after the last step) as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="control plane only (ranks, shards, timing reduction) on CPU/gloo; no engine")
     args = ap.parse_args()
@@ -440,6 +573,7 @@ def main():
         dist.broadcast_object_list(uid, src=0)
         eng.comm_init(uid[0], world, rank, timeout_s=600.0)  # a rank that never joins ends the run
         nranks = eng.comm_nranks()
+    start = sac_state(eng) if args.dump_outputs else None
 
     import torch
 
@@ -494,9 +628,11 @@ def main():
     # stream time per record, 0.2 ms per step at MT10/W400 (787 vs 587 us per step).  Eager: the
     # kernel timing comes from HIP events around every GEMM launch on the stream it runs on, over a
     # second pass of the same number of steps right after; a graph replay cannot carry events, so
-    # then it comes from one extra serialised step.
+    # then it comes from one extra serialised step.  Both belong to --full.
     live = mode != "graph"
     eng.set_timing(False)
+    if start:  # the timed steps start from the set-up's state and streams
+        sac_restore(eng, start)
     if dist:
         dist.barrier()
     torch.cuda.synchronize(local_rank)
@@ -514,49 +650,11 @@ def main():
         elapsed = float(t.item())
     logs = eng.logs()
     assert all(math.isfinite(v) for v in logs.values()), logs
-    events_ms = None
-    if live:  # the events pass: the same steps again, every GEMM launch bracketed by HIP events
-        eng.set_timing(True)
-        a = time.perf_counter()
-        eng.update_many(args.steps)
-        eng.synchronize()
-        events_ms = 1e3 * (time.perf_counter() - a) / args.steps
-        eng.set_timing(False)
-
-    # dominant-kernel roofline from the per-launch HIP events
-    names = dict(GEMM_FAMILIES["split3" if args.precision == "bf16" else args.precision])
-    fam = {f: eng.timing(f) for f in names} if live else None
-    # the same kernels solo: one extra step serialised on one stream.  Eager: context for the
-    # fraction (under the step's concurrency a launch shares the CUs with its neighbours).
-    # Graph: the replays carry no events, so this IS the measurement (rocprof's mean over the
-    # replays agrees within a few %).
-    eng.set_timing(True, serial=True)
-    eng.update_many(1)
-    eng.synchronize()
-    solo = {f: eng.timing(f) for f in names}
-    eng.set_timing(False)
-    for f in names:  # the kernel the engine actually launched for each family
-        k = eng.timing_kernel(f)
-        if k and k != "gemm_x3p_kernel":
-            names[f] = k + " (" + names[f].split(" (", 1)[1]
-    if fam is None:
-        fam = solo
-    timed_steps = args.steps if live else 1
-    dom = max(fam, key=lambda f: fam[f][0])
-    ms, nl, fl = fam[dom]
-    gemm_ms = sum(v[0] for v in fam.values()) / timed_steps
-    gemm_fl = sum(v[2] for v in fam.values()) / timed_steps
-    achieved = (fl / nl) / (ms / nl * 1e-3) / 1e12 if nl else 0.0
-    traffic, traffic_src = pmc_traffic(args.precision, dom, args.workload)
-    if args.precision == "split3":  # 6 bf16 MFMA products per fp32 multiply-add
-        peak, basis = BF16_MFMA_PEAK_TF / 6.0, "bf16 dense MFMA peak / 6 products (fp32-accurate split)"
-    elif args.precision == "split2h":  # 3 fp16 MFMA products (fp16 runs at the bf16 rate)
-        peak, basis = BF16_MFMA_PEAK_TF / 3.0, "fp16 dense MFMA peak / 3 products (fp32-accurate 2xfp16 split)"
-    elif args.precision == "bf16":
-        peak, basis = BF16_MFMA_PEAK_TF, "bf16 dense MFMA peak"
-    else:
-        peak, basis = FP32_MFMA_PEAK_TF, "f32-input MFMA dense peak"
-
+    if args.dump_outputs:  # what a caller of update_many reads back: the logs and the stepped networks
+        dump_outputs(args.dump_outputs, {"logs": np.array([logs[k] for k in L.LOG_KEYS], np.float64),
+                                         "actor": eng.get_params(L.ACTOR), "critic": eng.get_params(L.CRITIC),
+                                         "critic_target": eng.get_params(L.CRITIC_TARGET),
+                                         "log_alpha": eng.get_params(L.LOG_ALPHA)}, rank)
     flops = algorithmic_flops(T, W)
     sps = args.steps / elapsed
     out = dict(base)
@@ -565,36 +663,17 @@ def main():
         "ms_per_step": 1e3 * elapsed / args.steps,
         "settle_steps": settle,
         "nranks": nranks,
-        "roofline": {"bound": "mfma", "kernel": names[dom], "achieved": achieved,
-                     "peak": peak, "peak_basis": basis, "unit": "TFLOP/s", "frac": achieved / peak,
-                     "traffic": traffic, "traffic_unit": "HBM bytes per launch (rocprofv3 PMC, gfx950-corrected)",
-                     "traffic_source": traffic_src, "launches": nl, "avg_launch_us": 1e3 * ms / max(nl, 1),
-                     "algorithmic_flops_per_launch": fl / max(nl, 1),
-                     "timing": "HIP events per launch over a second pass of the timed eager steps (the "
-                               "timed pass runs without events)" if live
-                     else "graph replays carry no events: HIP events per launch in one serialised step",
-                     "events_pass_ms_per_step": events_ms,
-                     "clock": pmc_clock(args.precision, dom, args.workload),
-                     "solo": {"achieved": (solo[dom][2] / max(solo[dom][1], 1)) / (solo[dom][0] / max(solo[dom][1], 1) * 1e-3) / 1e12
-                              if solo[dom][0] else None,
-                              "avg_launch_us": 1e3 * solo[dom][0] / max(solo[dom][1], 1),
-                              "frac": ((solo[dom][2] / (solo[dom][0] * 1e-3) / 1e12) / peak) if solo[dom][0] else None,
-                              "timing": "one extra step with every kernel serialised on one stream"}},
         "step_flops": flops,
         "step_tflops_per_s": flops * sps / world / 1e12,
-        "gemm_kernel_ms_per_step": gemm_ms,  # sum of GEMM launch durations (they overlap across streams)
-        "gemm_tflops_per_s": gemm_fl / (gemm_ms * 1e-3) / 1e12 if gemm_ms else 0.0,
-        "gemm_families": {names[f]: {"ms_per_step": v[0] / timed_steps, "launches_per_step": v[1] / timed_steps,
-                                     "avg_launch_us": 1e3 * v[0] / max(v[1], 1),
-                                     "tflops": v[2] / (v[0] * 1e-3) / 1e12 if v[0] else 0.0}
-                          for f, v in fam.items()},
         "logs": logs,
     })
     out["config"] = dict(out["config"], exec=mode)
+    if args.full:
+        out.update(gemm_report(eng, args, live))
     eng.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(T, W, clip, args.cpu_steps, args.cpu_c0_steps)
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -51,6 +51,31 @@ def test_world_size_mismatch_is_an_error():
     assert p.returncode == 2 and "WORLD_SIZE" in p.stderr
 
 
+def test_dump_outputs_writes_flat_float_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 stays, the rest is float32, flat; an array above the cap is written as the
+    same sorted sample of its elements every time; ranks above 0 get their own file names."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 100)
+    big = np.arange(1000, dtype=np.float32).reshape(10, 100)
+    arrays = {"logs": np.array([1.5, 2.5]), "small": np.arange(6, dtype=np.int32).reshape(2, 3), "big": big}
+    bench.dump_outputs(str(tmp_path / "a"), arrays, 0)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, 1)
+    logs, small, a = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("logs", "small", "big"))
+    assert logs.dtype == np.float64 and logs.tolist() == [1.5, 2.5]
+    assert small.dtype == np.float32 and small.tolist() == [0, 1, 2, 3, 4, 5]
+    assert a.dtype == np.float32 and a.shape == (100,) and np.all(np.diff(a) > 0) and a.max() > 500
+    assert np.array_equal(a, np.load(tmp_path / "b" / "big.rank1.npy"))
+
+
+def test_full_and_dump_outputs_are_options_of_the_dry_run():
+    d = _line(_run(["--dry-run", "--full", "--dump-outputs", os.devnull]))
+    assert d["dry_run"] is True and d["steps"] == 50
+
+
 def test_pmc_traffic_takes_the_newest_round_summary(tmp_path, monkeypatch):
     """The roofline's `traffic` comes from the newest committed PMC summary of the workload: rounds in
     order, then a..z, aa..zz (r5x before r5bb), not plain name order."""

@@ -8,6 +8,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -rf --timeout 300 --tim
 rc=$?; echo "pytest exit $rc" >> $O/gpu_tests.log
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
-timeout -k 10 300 python bench.py --workload atari_drq > $O/bench_drq.json 2> $O/bench_drq.err || exit 1
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --workload atari_drq > $O/bench_drq.json 2> $O/bench_drq.err || exit 1
 echo done
