@@ -290,6 +290,34 @@ int mtsac_task_gradient_stats(mtsac_engine* h, int which, const float* threshold
                               float tau, double* gram, double* l1, int64_t* counts,
                               int64_t* near_zero);
 
+/* ---- PCGrad gradient surgery (PCGradConfig on both optimizers, mtrl/config/optim.py and
+ * mtrl/optim/pcgrad.py:38-134; the split losses of mtsac.py:513-711).  DESIGN.md section 9.
+ * mtsac_set_pcgrad: on = 1 makes mtsac_update / mtsac_update_many run the PCGrad step for BOTH networks
+ * (the only combination the reference runs): per-task gradients of critic and actor (mtsac_task_gradients'
+ * pass), surgery in Gram form, then the usual clip + Adam (+ Polyak).  Allocates the [T][P] matrices.
+ * -95 on a sharded engine or with use_task_weights, -22 for more than 64 tasks, -12 when the matrices do
+ * not fit.  The step is eager: mtsac_enable_graph(1) returns -95 while the mode is on.  Log slots 2 and 5
+ * hold the pre-surgery |mean_t g_t|, slot 7 the mean explore loss of the split actor loss.
+ * mtsac_pcgrad_set_order: pins the task orders (permutations of 0..T-1; jax.random.permutation of the
+ * reference) of the following steps; both NULL: back to per-step draws from the device noise stream.
+ * mtsac_pcgrad_get_order: the orders the last step used.
+ * mtsac_get_pcgrad_logs: out[0..4] the critic's PCGradState of the last step (n_grad_conflicts,
+ * avg_grad_magnitude, avg_grad_magnitude_before_surgery, avg_cosine_similarity,
+ * avg_cosine_similarity_diff; the last two NaN without cosine_sim_logs), out[5..9] the actor's.
+ * The kernels alone, on the matrix mtsac_set_task_gradients / mtsac_task_gradients left (which 0 = critic,
+ * 1 = actor): mtsac_task_gram: gram[T*T] = M M^T in fp64; mtsac_task_pcgrad_solve: Gram + solve with the
+ * order perm: w[T] (the combine weights, original task order) and logs[6] (the five values above, then
+ * |mean_t g_t|); mtsac_task_combine: sum_t w[t] M[t] (t ascending) written into the network's padded
+ * gradient buffer and read back leaf by leaf into out_dense[P]. */
+int mtsac_set_pcgrad(mtsac_engine* h, int32_t on, int32_t cosine_sim_logs);
+int mtsac_pcgrad_set_order(mtsac_engine* h, const int32_t* critic_perm, const int32_t* actor_perm);
+int mtsac_pcgrad_get_order(mtsac_engine* h, int32_t* critic_perm, int32_t* actor_perm);
+int mtsac_get_pcgrad_logs(mtsac_engine* h, float* out /* 10 */);
+int mtsac_task_gram(mtsac_engine* h, int which, double* gram);
+int mtsac_task_pcgrad_solve(mtsac_engine* h, int which, const int32_t* perm, int32_t cosine_sim_logs, float* w,
+                            float* logs /* 6 */);
+int mtsac_task_combine(mtsac_engine* h, int which, const float* w, float* out_dense);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,13 @@ SIGNATURES = {
     "mtsac_set_task_gradients": (ctypes.c_int, [P, ctypes.c_int, P, I64]),
     "mtsac_task_gradient_select": (ctypes.c_int, [P, ctypes.c_int, P, P]),
     "mtsac_task_gradient_stats": (ctypes.c_int, [P, ctypes.c_int, P, ctypes.c_float, ctypes.c_float, P, P, P, P]),
+    "mtsac_set_pcgrad": (ctypes.c_int, [P, I32, I32]),
+    "mtsac_pcgrad_set_order": (ctypes.c_int, [P, P, P]),
+    "mtsac_pcgrad_get_order": (ctypes.c_int, [P, P, P]),
+    "mtsac_get_pcgrad_logs": (ctypes.c_int, [P, P]),
+    "mtsac_task_gram": (ctypes.c_int, [P, ctypes.c_int, P]),
+    "mtsac_task_pcgrad_solve": (ctypes.c_int, [P, ctypes.c_int, P, I32, P, P]),
+    "mtsac_task_combine": (ctypes.c_int, [P, ctypes.c_int, P, P]),
     "mtsac_debug_gemm_bench": (ctypes.c_int, [ctypes.c_int] * 8 + [PD]),
     "mtsac_debug_gemm_x3p": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
     "mtsac_debug_gemm_x3p_bench": (ctypes.c_int, [ctypes.c_int] * 6 + [PD]),

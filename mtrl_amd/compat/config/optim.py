@@ -21,3 +21,17 @@ class OptimizerConfig:
     @property
     def adam_eps(self) -> float:  # config/optim.py:29-32
         return self.eps if self.eps is not None else 1e-5
+
+
+@dataclass(frozen=True, kw_only=True)
+class PCGradConfig(OptimizerConfig):
+    """config/optim.py:59-72: optax.chain(pcgrad(num_tasks, cosine_sim_logs), clip, adam).  The engine
+    runs the surgery in Gram form on the per-task gradients (mtrl_amd/csrc/pcgrad.hip); both the actor's
+    and the critic's optimizer must be PCGrad (the only combination the reference itself can run)."""
+
+    num_tasks: int
+    cosine_sim_logs: bool = False
+
+    @property
+    def requires_split_task_losses(self) -> bool:
+        return True

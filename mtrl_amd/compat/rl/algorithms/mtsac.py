@@ -5,7 +5,8 @@
 reference's functional signatures (``self, logs = self.update(data)``) while the state
 lives in one ``MTSACEngine`` (device memory, mutated in place; methods return ``self``).
 Supported: multi-head MLP actor/critic (MultiHeadConfig or VanillaNetworkConfig with
-num_tasks from the algorithm config), MSE critic, Adam optimizers -- the north-star path.
+num_tasks from the algorithm config), MSE critic, Adam optimizers -- the north-star path --
+and PCGrad gradient surgery on both networks (PCGradConfig, experiments/misc/mt10_mtmhsac_pcgrad.py).
 """
 
 from __future__ import annotations
@@ -16,10 +17,10 @@ from collections.abc import Mapping
 import numpy as np
 
 from .... import _lib as L
-from ....engine import MTSACEngine, make_config
+from ....engine import PCGRAD_LOG_KEYS, MTSACEngine, make_config
 from ....init import init_mtsac
 from ...config.networks import ContinuousActionPolicyConfig, QValueFunctionConfig
-from ...config.optim import OptimizerConfig
+from ...config.optim import OptimizerConfig, PCGradConfig
 from ...config.rl import AlgorithmConfig
 from ...config.utils import Activation, Initializer, Optimizer
 from ..buffers import MultiTaskReplayBuffer
@@ -43,12 +44,14 @@ class MTSACConfig(AlgorithmConfig):
 class _DeviceLogs(Mapping):
     """The update's LogDict, fetched from the device on first access (like jax.device_get)."""
 
-    def __init__(self, engine: MTSACEngine):
-        self._engine, self._d = engine, None
+    def __init__(self, engine: MTSACEngine, pcgrad: bool = False):
+        self._engine, self._d, self._pcgrad = engine, None, pcgrad
 
     def _get(self):
         if self._d is None:
             self._d = self._engine.logs()
+            if self._pcgrad:  # the PCGradState of both optimizers (mtrl/optim/pcgrad.py:12-17)
+                self._d.update(self._engine.pcgrad_logs())
         return self._d
 
     def __getitem__(self, k):
@@ -58,7 +61,7 @@ class _DeviceLogs(Mapping):
         return iter(self._get())
 
     def __len__(self):
-        return len(L.LOG_KEYS)
+        return len(L.LOG_KEYS) + (2 * len(PCGRAD_LOG_KEYS) if self._pcgrad else 0)
 
 
 def _check_supported(net, what: str):
@@ -68,8 +71,36 @@ def _check_supported(net, what: str):
         raise NotImplementedError(f"{what}: only he_uniform trunk init is implemented")
     if not getattr(net, "use_bias", True):
         raise NotImplementedError(f"{what}: use_bias=False is not implemented")
-    if net.optimizer.optimizer is not Optimizer.Adam or net.optimizer.requires_split_task_losses:
-        raise NotImplementedError(f"{what}: only plain Adam (optax.adam + clip_by_global_norm)")
+    split = net.optimizer.requires_split_task_losses and not isinstance(net.optimizer, PCGradConfig)
+    if net.optimizer.optimizer is not Optimizer.Adam or split:
+        raise NotImplementedError(f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad")
+
+
+def _check_pcgrad(config: "MTSACConfig", task_shard) -> bool:
+    """True when both optimizers are PCGrad; raises for what the engine's PCGrad step does not run."""
+    opt_a = config.actor_config.network_config.optimizer
+    opt_c = config.critic_config.network_config.optimizer
+    pa, pc = isinstance(opt_a, PCGradConfig), isinstance(opt_c, PCGradConfig)
+    if not (pa or pc):
+        return False
+    if pa != pc:
+        raise NotImplementedError(
+            "PCGrad on one network only: the reference itself cannot run it (mtsac.py:581 averages the critic's "
+            "per-task gradients unless the ACTOR's optimizer is PCGrad, and pcgrad's shape assert then fails); "
+            "give both actor and critic a PCGradConfig")
+    if opt_a.num_tasks != config.num_tasks or opt_c.num_tasks != config.num_tasks:
+        raise ValueError("PCGradConfig.num_tasks must equal the algorithm's num_tasks")
+    if opt_a.cosine_sim_logs != opt_c.cosine_sim_logs:
+        raise NotImplementedError("PCGrad: cosine_sim_logs must agree between actor and critic (one engine switch)")
+    if config.use_task_weights:
+        raise NotImplementedError(
+            "PCGrad with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
+            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
+    if task_shard is not None:
+        raise NotImplementedError(
+            "PCGrad on a task-sharded engine: the surgery needs every task's gradient of the whole network on "
+            "one engine (the Gram matrix couples all tasks)")
+    return True
 
 
 class MTSAC(OffPolicyAlgorithm):
@@ -83,16 +114,22 @@ class MTSAC(OffPolicyAlgorithm):
         self._buffer = None  # the replay buffer living in this engine, once spawned
         self.gamma, self.tau = config.gamma, config.tau
         self.target_entropy = -float(np.prod(env_config.action_space.shape))
+        self.pcgrad = False  # both optimizers PCGrad: the engine runs the gradient-surgery step
 
     # ------------------------------------------------------------------ construction
     @staticmethod
     def initialize(config: MTSACConfig, env_config, seed: int = 1, *, precision: str = "split2h",
-                   device: int = 0) -> "MTSAC":
+                   device: int = 0, task_shard: tuple[int, int] | None = None) -> "MTSAC":
+        """task_shard (first task, count): reserved -- this trainer runs unsharded engines (task sharding
+        is driven through mtrl_amd.shard)."""
         if config.critic_config.use_classification:
             raise NotImplementedError("classification critics are outside the MTSAC MSE path")
         net_a, net_c = config.actor_config.network_config, config.critic_config.network_config
         _check_supported(net_a, "actor")
         _check_supported(net_c, "critic")
+        pcgrad = _check_pcgrad(config, task_shard)
+        if task_shard is not None:
+            raise NotImplementedError("task sharding is driven through mtrl_amd.shard, not this trainer")
         T = config.num_tasks
         obs_dim = int(np.prod(env_config.observation_space.shape))
         act_dim = int(np.prod(env_config.action_space.shape))
@@ -109,6 +146,8 @@ class MTSAC(OffPolicyAlgorithm):
             batch_per_task=128, capacity=128, precision=L.PRECISIONS[precision], noise_seed=seed + 1,
         )
         eng = MTSACEngine(make_config(**kw), device=device)
+        if pcgrad:
+            eng.set_pcgrad(True, net_a.optimizer.cosine_sim_logs)
         a, q = init_mtsac(T, obs_dim, act_dim, net_a.width, net_a.depth, net_c.width, net_c.depth,
                           config.num_critics, seed=seed)
         eng.set_params(L.ACTOR, a)
@@ -116,7 +155,9 @@ class MTSAC(OffPolicyAlgorithm):
         eng.set_params(L.CRITIC_TARGET, q)
         print("Actor Params:", eng.param_count(L.ACTOR))
         print("Critic Params:", eng.param_count(L.CRITIC))
-        return MTSAC(config, env_config, seed, eng, kw)
+        agent = MTSAC(config, env_config, seed, eng, kw)
+        agent.pcgrad = pcgrad
+        return agent
 
     def _rebuild(self, **changes) -> None:
         """Re-create the engine with new batch / buffer geometry, keeping parameters, optimizer
@@ -132,6 +173,8 @@ class MTSAC(OffPolicyAlgorithm):
         old = self.engine
         self.engine = MTSACEngine(make_config(**self._cfg_kwargs), device=old.device)
         old.close()
+        if self.pcgrad:
+            self.engine.set_pcgrad(True, self.config.actor_config.network_config.optimizer.cosine_sim_logs)
         for w, v in keep.items():
             self.engine.set_params(w, v)
         for i, c in enumerate(counts):
@@ -188,13 +231,13 @@ class MTSAC(OffPolicyAlgorithm):
         if n != self._cfg_kwargs["batch_per_task"]:  # raises once a buffer lives in the engine
             self._rebuild(batch_per_task=n, capacity=max(self._cfg_kwargs["capacity"], n))
         self.engine.update(tuple(data))
-        return self, _DeviceLogs(self.engine)
+        return self, _DeviceLogs(self.engine, self.pcgrad)
 
     def update_from_buffer(self, replay_buffer, batch_size: int, want_logs: bool):
         if getattr(replay_buffer, "engine", None) is self.engine and batch_size // self.num_tasks == \
                 self._cfg_kwargs["batch_per_task"]:
             self.engine.update_many(1)  # device sampling + update, no host round trip
-            return self, _DeviceLogs(self.engine)
+            return self, _DeviceLogs(self.engine, self.pcgrad)
         return super().update_from_buffer(replay_buffer, batch_size, want_logs)
 
     def compute_weights(self, data):

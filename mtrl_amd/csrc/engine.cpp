@@ -1774,51 +1774,7 @@ struct mtsac_engine {
       // temperature (mtsac.py:713-731), post-update parameter norms (trunk |p|^2 replicated, head
       // |p|^2 summed over shards), logs: one launch
       allreduce(pn + 2, 2);
-      StepFinish f{};
-      if (!sharded()) {
-        f.rows[0] = row_a;
-        f.row_out[0] = critic.g + critic.n_flat + 1;
-        f.rows[1] = row_b;
-        f.row_out[1] = critic.g + critic.n_flat + 2;
-        f.rows[2] = row_c;
-        f.row_out[2] = actor.g + actor.n_flat + 1;
-      }
-      f.B = Bl;
-      f.alpha = al;
-      f.alpha_grad = sharded() ? 0 : 1;
-      f.lr = cfg.alpha_lr;
-      f.b1 = cfg.adam_b1;
-      f.b2 = cfg.adam_b2;
-      f.eps = cfg.adam_eps;
-      f.max_norm = cfg.alpha_max_grad_norm;
-      Net* nets[2] = {&critic, &actor};
-      for (int w = 0; w < 2; ++w) {
-        f.pn.pt[w] = nets[w]->ppt;
-        f.pn.nt[w] = nets[w]->n_ppt;
-        f.pn.ph[w] = nets[w]->pph;
-        f.pn.nh[w] = nets[w]->n_pph;
-        f.pn.sc[w] = nets[w]->sc;
-      }
-      f.head_sq = sharded() ? pn + 2 : nullptr;
-      LogParams& lp = f.logs;
-      lp.critic_sums = critic.g + critic.n_flat + 1;
-      lp.actor_sums = actor.g + actor.n_flat + 1;
-      lp.critic = critic.sc;
-      lp.actor = actor.sc;
-      lp.alpha_loss_sum = actor.g + actor.n_flat + 2;
-      lp.log_alpha = log_alpha;
-      lp.T_glob = T_g;
-      lp.inv_critic = 1.0f / ((float)critic.E * (float)B_glob);
-      lp.inv_actor = 1.0f / (float)B_glob;
-      lp.inv_b = 1.0f / (float)B_glob;
-      lp.logs = logs;
-      f.counter = counter;
-      if (h2) {  // the optimizers' weight maxima into the records (the next updates' plane exponents)
-        f.wmax[0] = WeightMaxJob{wparts[0], wgrid[0], wbh[0], r_w[0][0].d};
-        f.wmax[1] = WeightMaxJob{wparts[1], wgrid[1], wbh[1], r_w[1][0].d};
-        f.wmax[2] = WeightMaxJob{tparts, wgrid[1], -1, r_w[1][1].d};
-        f.nwmax = 3;
-      }
+      StepFinish f = finish_params(al);
       step_finish(f, cur);
     });
     if (pipelined) (void)hipEventRecord(ev_tail[step_par], segs[s_tail].lane);
@@ -1916,8 +1872,9 @@ struct mtsac_engine {
                         net.E, T_l, (long long)net.width * net.hd, cur);
   }
 
-  void task_grads(bool device_batch, bool device_noise) {
-    const int Bl = B, n_rows = B / T_l;
+  // the batch into the input buffers, its row lists; rows must be interleaved i*T + t
+  void tg_prepare(bool device_batch) {
+    const int Bl = B;
     cur = st;
     cur_lane = 0;
     counts = inset[inset_cur].counts;  // task_rows below (check_interleaved holds the layout)
@@ -1933,9 +1890,11 @@ struct mtsac_engine {
     check_interleaved(task, Bl, T_l, err, cur);
     task_rows(task, Bl, T_l, counts, rows, Bl, cur);
     if (cfg.use_task_weights) row_alpha(task, cfg.task_begin, log_alpha, T_g, Bl, 1, row_c, tw, cur);
-    const float* twp = cfg.use_task_weights ? tw : nullptr;
-    for (int w = 0; w < 2; ++w) (void)hipMemsetAsync(tg[w], 0, sizeof(float) * T_l * tgP[w], cur);
-    PolicyParams pp{};
+  }
+
+  void tg_params(PolicyParams& pp, CriticHeadParams& ch) {
+    const int Bl = B, n_rows = B / T_l;
+    pp = PolicyParams{};
     pp.seed = cfg.noise_seed;
     pp.counter = counter;
     pp.A = A;
@@ -1947,16 +1906,32 @@ struct mtsac_engine {
     pp.max_rows = Bl;
     pp.T_l = T_l;
     pp.max_count = n_rows;
-    CriticHeadParams ch{};
+    ch = CriticHeadParams{};
     ch.rew = rew;
     ch.done = done;
     ch.log_alpha = log_alpha;
     ch.task = task;
     ch.task_begin = cfg.task_begin;
-    ch.tw = twp;
+    ch.tw = cfg.use_task_weights ? tw : nullptr;
     ch.gamma = cfg.gamma;
     ch.clip = cfg.clip;
     ch.T_glob = T_g;
+  }
+
+  void task_grads(bool device_batch, bool device_noise) {
+    tg_prepare(device_batch);
+    for (int w = 0; w < 2; ++w) (void)hipMemsetAsync(tg[w], 0, sizeof(float) * T_l * tgP[w], cur);
+    tg_critic(device_noise, false);
+    tg_actor(device_noise, false);
+  }
+
+  // pc: the PCGrad training step's form (pcgrad_step): its own noise streams, one draw per row index i
+  // shared by the tasks, and (actor) the explore term of the split loss
+  void tg_critic(bool device_noise, bool pc) {
+    const int Bl = B, n_rows = B / T_l;
+    PolicyParams pp;
+    CriticHeadParams ch;
+    tg_params(pp, ch);
     const int Dc = critic.depth, Da = actor.depth;
 
     // ---- critic (mtsac.py:1000-1048): a_n ~ pi(.|s), y from the target critic at (s', a_n)
@@ -1965,7 +1940,8 @@ struct mtsac_engine {
       PolicyParams q = pp;
       q.head = head(actor, actor.p, han[Da - 1], Bl, task);
       q.eps = device_noise ? nullptr : eps_n;
-      q.stream_id = 3;
+      q.stream_id = pc ? 5 : 3;
+      q.noise_div = pc ? T_l : 0;
       q.a_out = xcn;
       q.logpi = logpi_n;
       policy_head(q, cur);
@@ -2000,13 +1976,22 @@ struct mtsac_engine {
       if (i > 0) dgrad_layer(critic, critic.p, hc, nullptr, dzc, nullptr, i, Bl);
     }
 
+  }
+
+  void tg_actor(bool device_noise, bool pc) {
+    const int Bl = B, n_rows = B / T_l;
+    PolicyParams pp;
+    CriticHeadParams ch;
+    tg_params(pp, ch);
+    const int Dc = critic.depth, Da = actor.depth;
     // ---- actor (mtsac.py:1051-1090): the current critic, per-task mean over n rows
     trunk_forward(actor, actor.p, 0, xa, ld_a, ha, nullptr, Bl);
     {
       PolicyParams q = pp;
       q.head = head(actor, actor.p, ha[Da - 1], Bl, task);
       q.eps = device_noise ? nullptr : eps_c;
-      q.stream_id = 4;
+      q.stream_id = pc ? 6 : 4;
+      q.noise_div = pc ? T_l : 0;
       q.a_out = xcp;
       q.logpi = logpi;
       q.cache = cache;
@@ -2041,6 +2026,13 @@ struct mtsac_engine {
       ag.ls_min = cfg.log_std_min;
       ag.ls_max = cfg.log_std_max;
       ag.dout = dout_a;
+      if (pc) {  // mtsac.py:668-673 with the default _explore = True of the split call (:678-682)
+        ag.a_data = xc;
+        ag.ld_a_data = ld_c;
+        ag.explore_scale = 2.0f / ((float)n_rows * (float)A);
+        ag.row_loss = row_c;
+        ag.row_explore = pc_row_e;
+      }
       action_grad(ag, cur);
     }
     const HeadParams ahp = head(actor, actor.p, ha[Da - 1], Bl, task);
@@ -2051,6 +2043,149 @@ struct mtsac_engine {
       task_wgrad(actor, 1, xa, ld_a, ha, dza, i);
       if (i > 0) dgrad_layer(actor, actor.p, ha, nullptr, dza, nullptr, i, Bl);
     }
+  }
+
+  // the step's scalar tail (step_finish): loss sums, temperature update, parameter norms, logs
+  StepFinish finish_params(const AlphaParams& al) {
+    const int Bl = B;
+    StepFinish f{};
+    if (!sharded()) {
+      f.rows[0] = row_a;
+      f.row_out[0] = critic.g + critic.n_flat + 1;
+      f.rows[1] = row_b;
+      f.row_out[1] = critic.g + critic.n_flat + 2;
+      f.rows[2] = row_c;
+      f.row_out[2] = actor.g + actor.n_flat + 1;
+    }
+    f.B = Bl;
+    f.alpha = al;
+    f.alpha_grad = sharded() ? 0 : 1;
+    f.lr = cfg.alpha_lr;
+    f.b1 = cfg.adam_b1;
+    f.b2 = cfg.adam_b2;
+    f.eps = cfg.adam_eps;
+    f.max_norm = cfg.alpha_max_grad_norm;
+    Net* nets[2] = {&critic, &actor};
+    for (int w = 0; w < 2; ++w) {
+      f.pn.pt[w] = nets[w]->ppt;
+      f.pn.nt[w] = nets[w]->n_ppt;
+      f.pn.ph[w] = nets[w]->pph;
+      f.pn.nh[w] = nets[w]->n_pph;
+      f.pn.sc[w] = nets[w]->sc;
+    }
+    f.head_sq = sharded() ? pn + 2 : nullptr;
+    LogParams& lp = f.logs;
+    lp.critic_sums = critic.g + critic.n_flat + 1;
+    lp.actor_sums = actor.g + actor.n_flat + 1;
+    lp.critic = critic.sc;
+    lp.actor = actor.sc;
+    lp.alpha_loss_sum = actor.g + actor.n_flat + 2;
+    lp.log_alpha = log_alpha;
+    lp.T_glob = T_g;
+    lp.inv_critic = 1.0f / ((float)critic.E * (float)B_glob);
+    lp.inv_actor = 1.0f / (float)B_glob;
+    lp.inv_b = 1.0f / (float)B_glob;
+    lp.logs = logs;
+    f.counter = counter;
+    if (h2) {  // the optimizers' weight maxima into the records (the next updates' plane exponents)
+      f.wmax[0] = WeightMaxJob{wparts[0], wgrid[0], wbh[0], r_w[0][0].d};
+      f.wmax[1] = WeightMaxJob{wparts[1], wgrid[1], wbh[1], r_w[1][0].d};
+      f.wmax[2] = WeightMaxJob{tparts, wgrid[1], -1, r_w[1][1].d};
+      f.nwmax = 3;
+    }
+    return f;
+  }
+
+  // ------------------------------------------------------------ PCGrad training step
+  // Both optimizers as the reference's PCGradConfig chain (mtrl/config/optim.py, mtrl/optim/pcgrad.py):
+  // pcgrad -> clip_by_global_norm -> adam.  The per-task gradients come from the eval metrics' pass
+  // (task_grads' halves); the surgery runs in Gram form (pcgrad.hip) and leaves mean_i g_i^pc in Net::g,
+  // so optimize() -- clip, Adam, Polyak, planes -- runs unchanged.  Eager, on the main stream.
+  bool pc_on = false, pc_cos = false, pc_pinned = false, pc_graph_before = true;
+  double *pc_gram = nullptr, *pc_c = nullptr;
+  float *pc_w = nullptr, *pc_logs = nullptr, *pc_row_e = nullptr;  // [2][64], [2][8] (0 critic, 1 actor), [B]
+  int *pc_perm = nullptr, *pc_pin = nullptr;                       // [2][64] orders used / pinned
+
+  int ensure_pcgrad_buffers() {
+    int rc = 0;
+    if (pc_gram) return 0;
+    if ((rc = alloc(&pc_gram, 64 * 64)) || (rc = alloc(&pc_c, 64 * 64)) || (rc = alloc(&pc_w, 2 * 64)) ||
+        (rc = alloc(&pc_logs, 2 * 8)) || (rc = alloc(&pc_row_e, (size_t)B)) || (rc = alloc(&pc_perm, 2 * 64)) ||
+        (rc = alloc(&pc_pin, 2 * 64)))
+      return rc;
+    return hipDeviceSynchronize() == hipSuccess ? 0 : fail(-5, "device synchronize");
+  }
+
+  PcgradLeaves pc_leaves(const Net& net) const {
+    PcgradLeaves lv{};
+    const std::vector<long long> off = dense_offsets(net);
+    lv.n = (int)net.leaves.size();
+    for (int k = 0; k < lv.n; ++k) {
+      lv.dense[k] = off[k];
+      lv.padded[k] = net.leaves[k].first;
+    }
+    return lv;
+  }
+
+  void pc_gram_of(int w) {
+    task_gram(tg[w], T_l, tgP[w], task_gram_parts(tgP[w], PS_GRID), ps_gram_part, pc_gram, cur);
+  }
+
+  void pc_solve_of(int w, const int* pinned, bool cosine) {
+    PcgradSolve s{};
+    s.gram = pc_gram;
+    s.T = T_l;
+    s.pinned = pinned;
+    s.seed = cfg.noise_seed;
+    s.counter = counter;
+    s.stream_id = 7 + w;
+    s.cosine_logs = cosine ? 1 : 0;
+    s.ws_c = pc_c;
+    s.perm_out = pc_perm + 64 * w;
+    s.w = pc_w + 64 * w;
+    s.logs = pc_logs + 8 * w;
+    pcgrad_solve(s, cur);
+  }
+
+  // Gram, solve, combine of network w (0 critic, 1 actor): Net::g = mean_i g_i^pc
+  void pc_surgery(Net& net, int w) {
+    pc_gram_of(w);
+    pc_solve_of(w, pc_pinned ? pc_pin + 64 * w : nullptr, pc_cos);
+    task_combine(tg[w], pc_w + 64 * w, T_l, tgP[w], pc_leaves(net), net.g, cur);
+  }
+
+  // the other tasks' head blocks of every row stay zero: only the rows' head ranges are cleared (the
+  // trunk leaves are stored whole by the per-task weight grads)
+  void pc_clear_heads(const Net& net, int w) {
+    const std::vector<long long> off = dense_offsets(net);
+    (void)hipMemset2DAsync(tg[w], sizeof(float) * tgP[w], 0, sizeof(float) * off[2], T_l, cur);
+  }
+
+  void pcgrad_step(bool device_batch, bool device_noise) {
+    segs.clear();
+    actor.fin_sink.n = critic.fin_sink.n = 0;
+    zstep[0] = zstep[1] = false;
+    have_prev = false;
+    tg_prepare(device_batch);
+    // critic (mtsac.py:513-621, split losses): per-task gradients, surgery, clip + Adam + Polyak
+    pc_clear_heads(critic, 0);
+    tg_critic(device_noise, true);
+    pc_surgery(critic, 0);
+    optimize(critic, cfg.critic_lr, cfg.critic_max_grad_norm, true, 0);
+    refresh_wt(critic, critic.p, 0, cur, true);
+    refresh_wt(critic, critic.tgt, 1, cur, true);
+    // actor through the UPDATED critic (mtsac.py:623-711)
+    pc_clear_heads(actor, 1);
+    tg_actor(device_noise, true);
+    pc_surgery(actor, 1);
+    optimize(actor, cfg.actor_lr, cfg.actor_max_grad_norm, false, 1);
+    refresh_wt(actor, actor.p, 0, cur, true);
+    // temperature, parameter norms, logs; then the slots the surgery changes: the gradient magnitudes
+    // are the pre-surgery |mean_t g_t| (the optimizer's clip saw the combined gradient's norm)
+    StepFinish f = finish_params(alpha_params());
+    step_finish(f, cur);
+    pcgrad_logs(pc_logs, pc_logs + 8, pc_row_e, B, logs, cur);
+    cur = st;
   }
 
   AlphaParams alpha_params() {
@@ -2914,7 +3049,12 @@ int mtsac_update(mtsac_engine* h, const mtsac_batch* b, const float* eps_next, c
     HIP_TRY(hipMemcpyAsync(h->eps_c, eps_cur, sizeof(float) * B * A, hipMemcpyDefault, h->st));
   }
   h->tl_next = 0;
-  h->step(b == nullptr, eps_next == nullptr);
+  if (h->pc_on) {
+    if (h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
+    h->pcgrad_step(b == nullptr, eps_next == nullptr);
+  } else {
+    h->step(b == nullptr, eps_next == nullptr);
+  }
   HIP_TRY(hipGetLastError());
   if (b || eps_next) HIP_TRY(hipStreamSynchronize(h->st));  // borrowed host pointers
   return 0;
@@ -3035,10 +3175,146 @@ int mtsac_task_gradient_stats(mtsac_engine* h, int which, const float* threshold
   return 0;
 }
 
+// ---------------------------------------------------------------- PCGrad
+int mtsac_set_pcgrad(mtsac_engine* h, int32_t on, int32_t cosine_sim_logs) {
+  if (!h) return fail(-22, "null engine");
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->pc_on) h->use_graph = h->pc_graph_before;
+    h->pc_on = false;
+    return 0;
+  }
+  if (h->T_l != h->T_g || h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
+  if (h->cfg.use_task_weights)
+    return fail(-95, "PCGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
+  if (h->T_l > 64) return fail(-22, "PCGrad: at most 64 tasks");
+  int rc = h->ensure_task_grad_buffers();
+  if (!rc) rc = h->ensure_pcgrad_buffers();
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  if (h->gexec) {  // a captured plain step is not this mode's step
+    (void)hipGraphExecDestroy(h->gexec);
+    (void)hipGraphDestroy(h->graph);
+    h->gexec = nullptr;
+    h->graph = nullptr;
+  }
+  if (!h->pc_on) h->pc_graph_before = h->use_graph;
+  h->use_graph = false;
+  h->pc_on = true;
+  h->pc_cos = cosine_sim_logs != 0;
+  return 0;
+}
+
+static bool is_perm(const int32_t* p, int T) {
+  bool seen[64] = {};
+  for (int k = 0; k < T; ++k) {
+    if (p[k] < 0 || p[k] >= T || seen[p[k]]) return false;
+    seen[p[k]] = true;
+  }
+  return true;
+}
+
+int mtsac_pcgrad_set_order(mtsac_engine* h, const int32_t* critic_perm, const int32_t* actor_perm) {
+  if (!h) return fail(-22, "null engine");
+  if (!h->pc_gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
+  if ((critic_perm == nullptr) != (actor_perm == nullptr)) return fail(-22, "pin both orders or neither");
+  HIP_TRY(hipStreamSynchronize(h->st));
+  if (!critic_perm) {
+    h->pc_pinned = false;
+    return 0;
+  }
+  const int T = h->T_l;
+  if (!is_perm(critic_perm, T) || !is_perm(actor_perm, T)) return fail(-22, "an order must be a permutation of 0..T-1");
+  HIP_TRY(hipMemcpy(h->pc_pin, critic_perm, sizeof(int) * T, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->pc_pin + 64, actor_perm, sizeof(int) * T, hipMemcpyHostToDevice));
+  h->pc_pinned = true;
+  return 0;
+}
+
+int mtsac_pcgrad_get_order(mtsac_engine* h, int32_t* critic_perm, int32_t* actor_perm) {
+  if (!h || !critic_perm || !actor_perm) return fail(-22, "null argument");
+  if (!h->pc_gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
+  HIP_TRY(hipStreamSynchronize(h->st));
+  HIP_TRY(hipMemcpy(critic_perm, h->pc_perm, sizeof(int) * h->T_l, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(actor_perm, h->pc_perm + 64, sizeof(int) * h->T_l, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mtsac_get_pcgrad_logs(mtsac_engine* h, float* out) {
+  if (!h || !out) return fail(-22, "null argument");
+  if (!h->pc_gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
+  float l[16];
+  HIP_TRY(hipMemcpyAsync(l, h->pc_logs, sizeof(l), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  for (int w = 0; w < 2; ++w)
+    for (int k = 0; k < 5; ++k) out[5 * w + k] = l[8 * w + k];
+  return h->check_err();
+}
+
+int mtsac_task_gram(mtsac_engine* h, int which, double* gram) {
+  int rc = task_grad_ready(h, which);
+  if (rc) return rc;
+  if (!gram) return fail(-22, "null argument");
+  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  h->cur = h->st;
+  h->pc_gram_of(which);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(gram, h->pc_gram, sizeof(double) * h->T_l * h->T_l, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  return 0;
+}
+
+int mtsac_task_pcgrad_solve(mtsac_engine* h, int which, const int32_t* perm, int32_t cosine_sim_logs, float* w,
+                            float* logs) {
+  int rc = task_grad_ready(h, which);
+  if (rc) return rc;
+  if (!perm || !w || !logs) return fail(-22, "null argument");
+  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  const int T = h->T_l;
+  if (!is_perm(perm, T)) return fail(-22, "an order must be a permutation of 0..T-1");
+  if (h->pc_pinned) return fail(-16, "orders are pinned for the training step (mtsac_pcgrad_set_order(NULL, NULL) first)");
+  HIP_TRY(hipStreamSynchronize(h->st));
+  HIP_TRY(hipMemcpy(h->pc_pin + 64 * which, perm, sizeof(int) * T, hipMemcpyHostToDevice));
+  h->cur = h->st;
+  h->pc_gram_of(which);
+  h->pc_solve_of(which, h->pc_pin + 64 * which, cosine_sim_logs != 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(w, h->pc_w + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(logs, h->pc_logs + 8 * which, sizeof(float) * 6, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  return 0;
+}
+
+int mtsac_task_combine(mtsac_engine* h, int which, const float* w, float* out_dense) {
+  int rc = task_grad_ready(h, which);
+  if (rc) return rc;
+  if (!w || !out_dense) return fail(-22, "null argument");
+  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  Net& net = which == 0 ? h->critic : h->actor;
+  HIP_TRY(hipMemcpyAsync(h->pc_w + 64 * which, w, sizeof(float) * h->T_l, hipMemcpyHostToDevice, h->st));
+  h->cur = h->st;
+  task_combine(h->tg[which], h->pc_w + 64 * which, h->T_l, h->tgP[which], h->pc_leaves(net), net.g, h->st);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->st));
+  long long o = 0;  // the padded gradient buffer's leaves, as mtsac_get_params reads a parameter vector
+  for (auto& lf : net.leaves) {
+    HIP_TRY(hipMemcpy(out_dense + o, net.g + lf.first, sizeof(float) * lf.second, hipMemcpyDefault));
+    o += lf.second;
+  }
+  return 0;
+}
+
 int mtsac_update_many(mtsac_engine* h, int32_t steps) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
   if (steps <= 0) return 0;
+  if (h->pc_on) {  // eager, one stream, no overlap between steps; the task orders are drawn on the device
+    if (h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
+    h->tl_next = 0;
+    for (int s = 0; s < steps; ++s) h->pcgrad_step(true, true);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   if (!h->use_graph || h->timing || h->hook || h->chook) {  // events / host hooks need eager issue
     h->tl_next = 0;  // timing records every launch of this call
     // consecutive steps overlap (the last one joins every lane into the main stream); host hooks
@@ -3081,6 +3357,7 @@ int mtsac_get_logs(mtsac_engine* h, float* logs) {
 
 int mtsac_enable_graph(mtsac_engine* h, int32_t enable) {
   if (!h) return fail(-22, "null engine");
+  if (enable && h->pc_on) return fail(-95, "the PCGrad step is not captured: graph replay is unavailable in this mode");
   h->use_graph = enable != 0;
   return 0;
 }

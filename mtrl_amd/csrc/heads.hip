@@ -156,7 +156,8 @@ __device__ inline void policy_finish(const PolicyParams& p, int b, int t, const 
       eps = eps_in;
     } else {
       float nz[4];
-      normal4(p.seed, p.stream_id + 16u * (uint32_t)(lane >> 2), *p.counter, (uint32_t)b, nz);
+      const uint32_t nrow = p.noise_div > 0 ? (uint32_t)(b / p.noise_div) : (uint32_t)b;
+      normal4(p.seed, p.stream_id + 16u * (uint32_t)(lane >> 2), *p.counter, nrow, nz);
       eps = nz[lane & 3];
     }
     const float lsc = fminf(fmaxf(ls, p.ls_min), p.ls_max);
@@ -963,11 +964,21 @@ __device__ inline float action_grad_rows(const ActionGradParams& p, int b0, int 
     const int b = b0 + r;
 #pragma unroll
     for (int j = 0; j < AM; ++j) ga[r][j] = j < A ? wsum(ga[r][j]) : 0.f;
+    float ex_d = 0.f;  // explore term (split actor loss): a_data - a of this lane's action dimension
+    if (p.a_data != nullptr) {
+      if (b < p.B && lane < A) ex_d = p.a_data[(long long)rows[r] * p.ld_a_data + lane] - c_a[r];
+      const float ex = wsum(ex_d * ex_d) / (float)A;
+      if (b < p.B && lane == 0) {
+        p.row_loss[b] = p.row_loss[b] - ex;
+        p.row_explore[b] = ex;
+      }
+    }
     if (b >= p.B || lane >= A) continue;
     float g_a = 0.f;
 #pragma unroll
     for (int j = 0; j < AM; ++j)
       if (j == lane) g_a = ga[r][j];
+    if (p.a_data != nullptr) g_a = g_a + p.explore_scale * ex_d;
     const float ls = c_ls[r], a = c_a[r], eps = c_eps[r];
     const float g_logpi = c_lp[r];
     const float sigma = expf(fminf(fmaxf(ls, p.ls_min), p.ls_max));

@@ -312,6 +312,8 @@ struct PolicyParams {
   const int* rows;
   int max_rows, T_l;    // row-list stride, local tasks
   int max_count;        // bound on counts[] (sizes the grid)
+  int noise_div;        // > 0: device noise of row b is drawn for row b / noise_div (rows i*T + t share the
+                        // draw of i: the reference's vmap over tasks hands every task the same key)
 };
 void policy_head(const PolicyParams& p, hipStream_t st);
 // WhT[t][o][w] = Wh[t][w][o] for T_l tasks (E = 1): the policy heads' copy, after every write of Wh
@@ -397,6 +399,14 @@ struct ActionGradParams {
   float* dout;          // [B][2A]
   PlaneRec* dout_rec;   // split2h: per-workgroup max |dout| (the head backward's bound input), or null
   int* dout_parts;      // host: how many the launch wrote
+  // explore term of the split actor loss (mtsac.py:668-673): loss_t -= mean over the task's n x A entries of
+  // (a_data - a)^2.  a_data non-null: d/da of it (times explore_scale = 2 / (n A)) joins the critic's action
+  // grad, the row's term sum_j (a_data - a)^2 / A is taken off row_loss[b] and stored in row_explore[b]
+  const float* a_data;  // [B][ld_a_data] logged actions
+  int ld_a_data;
+  float explore_scale;
+  float* row_loss;
+  float* row_explore;
 };
 void action_grad(const ActionGradParams& p, hipStream_t st);
 
@@ -588,5 +598,40 @@ void scatter_task_blocks(const float* src, long long src_off, long long src_ms, 
                          long long dst_off, long long dst_ms, int E, int T, long long blk, hipStream_t st);
 // *err |= 1 unless task[r] == r % T_l for every row (rows interleaved i*T + t, as the buffer samples)
 void check_interleaved(const int* task, int B, int T_l, int* err, hipStream_t st);
+
+// ------------------------------------------------------------------ PCGrad in Gram form (pcgrad.hip;
+// mtrl/optim/pcgrad.py:38-134).  M: per-task gradients [T][P] (flax ravel order, T <= 64).
+// gram[T*T] (fp64) = M M^T: one partial [64*64] per workgroup in ws_part (nparts of them at most,
+// task_gram_parts), summed in order
+int task_gram_parts(long long P, int max_parts);
+void task_gram(const float* M, int T, long long P, int nparts, double* ws_part, double* gram, hipStream_t st);
+struct PcgradSolve {
+  const double* gram;   // [T*T]
+  int T;
+  const int* pinned;    // device [T] task order, or null: Fisher-Yates from uniform4(seed, stream_id, *counter, .)
+  unsigned long long seed;
+  const unsigned long long* counter;
+  unsigned int stream_id;
+  int cosine_logs;
+  double* ws_c;         // [64*64] workspace (the coefficient matrix C)
+  int* perm_out;        // [T] the order used
+  float* w;             // [T] combine weights mean_i C[i][t], original task order
+  float* logs;          // [6]: n_grad_conflicts, avg_grad_magnitude, avg_grad_magnitude_before_surgery,
+                        // avg_cosine_similarity, avg_cosine_similarity_diff (NaN without cosine_logs),
+                        // |mean_t g_t| (the pre-surgery norm)
+};
+void pcgrad_solve(const PcgradSolve& s, hipStream_t st);
+// out[padded[k] + i] = sum_t w[t] M[t][dense[k] + i] (t ascending, unfused multiply-adds) for every leaf k:
+// dense = the leaf's offset in a row of M, padded = its offset in out (Net::g)
+struct PcgradLeaves {
+  int n;
+  long long dense[18], padded[18];
+};
+void task_combine(const float* M, const float* w, int T, long long P, const PcgradLeaves& lv, float* out,
+                  hipStream_t st);
+// the PCGrad step's log slots: logs[2] / logs[5] = the pre-surgery norms (solve logs [5]), logs[7] = sum
+// row_explore / B
+void pcgrad_logs(const float* solve_critic, const float* solve_actor, const float* row_explore, int B, float* logs,
+                 hipStream_t st);
 
 }  // namespace mtsac

@@ -15,6 +15,10 @@ import numpy as np
 from . import _lib
 from ._lib import LOG_KEYS, Batch, Config, MTSACError, check
 
+# PCGradState fields (mtrl/optim/pcgrad.py:12-17), the order of mtsac_get_pcgrad_logs per network
+PCGRAD_LOG_KEYS = ("n_grad_conflicts", "avg_grad_magnitude", "avg_grad_magnitude_before_surgery",
+                   "avg_cosine_similarity", "avg_cosine_similarity_diff")
+
 
 def _ptr(x) -> tuple[int, Any]:
     """(address, keep-alive) of a host numpy array or a torch tensor (host or device)."""
@@ -237,6 +241,50 @@ class MTSACEngine:
                                                  l1.ctypes.data, counts.ctypes.data, nz.ctypes.data))
         return {"gram": gram, "l1": l1, "conflict": counts[0], "intersection": counts[1], "genuine": counts[2],
                 "mismatch": counts[3], "near_zero": nz}
+
+    # ------------------------------------------------------------------ PCGrad (include/mtsac.h)
+    def set_pcgrad(self, on: bool, cosine_sim_logs: bool = False) -> None:
+        """PCGrad on both optimizers: update / update_many run the gradient-surgery step."""
+        check(self.lib.mtsac_set_pcgrad(self._h, 1 if on else 0, 1 if cosine_sim_logs else 0))
+
+    def pcgrad_set_order(self, critic_perm=None, actor_perm=None) -> None:
+        """Pin the task orders of the following steps; None, None: device draws."""
+        if critic_perm is None and actor_perm is None:
+            check(self.lib.mtsac_pcgrad_set_order(self._h, None, None))
+            return
+        c = np.ascontiguousarray(critic_perm, np.int32).reshape(self.T_l)
+        a = np.ascontiguousarray(actor_perm, np.int32).reshape(self.T_l)
+        check(self.lib.mtsac_pcgrad_set_order(self._h, c.ctypes.data, a.ctypes.data))
+
+    def pcgrad_get_order(self) -> tuple[np.ndarray, np.ndarray]:
+        c, a = np.empty(self.T_l, np.int32), np.empty(self.T_l, np.int32)
+        check(self.lib.mtsac_pcgrad_get_order(self._h, c.ctypes.data, a.ctypes.data))
+        return c, a
+
+    def pcgrad_logs(self) -> dict[str, float]:
+        out = np.empty(2 * len(PCGRAD_LOG_KEYS), np.float32)
+        check(self.lib.mtsac_get_pcgrad_logs(self._h, out.ctypes.data))
+        return {f"metrics/{net}_{k}": float(out[5 * w + i])
+                for w, net in enumerate(("critic", "actor")) for i, k in enumerate(PCGRAD_LOG_KEYS)}
+
+    def task_gram(self, which: int) -> np.ndarray:
+        g = np.empty((self.T_l, self.T_l), np.float64)
+        check(self.lib.mtsac_task_gram(self._h, which, g.ctypes.data))
+        return g
+
+    def task_pcgrad_solve(self, which: int, perm, cosine_sim_logs: bool = False):
+        """(w [T] float32, logs: the five PCGradState values and ``grad_magnitude``) of the device solve."""
+        p = np.ascontiguousarray(perm, np.int32).reshape(self.T_l)
+        w, logs = np.empty(self.T_l, np.float32), np.empty(6, np.float32)
+        check(self.lib.mtsac_task_pcgrad_solve(self._h, which, p.ctypes.data, 1 if cosine_sim_logs else 0,
+                                               w.ctypes.data, logs.ctypes.data))
+        return w, {k: float(v) for k, v in zip(PCGRAD_LOG_KEYS + ("grad_magnitude",), logs)}
+
+    def task_combine(self, which: int, w) -> np.ndarray:
+        w = np.ascontiguousarray(w, np.float32).reshape(self.T_l)
+        out = np.empty(self.task_gradient_size(which), np.float32)
+        check(self.lib.mtsac_task_combine(self._h, which, w.ctypes.data, out.ctypes.data))
+        return out
 
     def update_many(self, steps: int) -> None:
         check(self.lib.mtsac_update_many(self._h, steps))
