@@ -81,6 +81,40 @@ int mtsac_debug_drq_wgrad_blocks(int cap);
 // residual), 1 data gradient (mask, residual), 2 weight-gradient partials.  -22 bad arguments.
 int mtsac_debug_drq_conv_bench(int kind, int B, int H, int W, int ci, int co, int iters, double* us_per_launch);
 
+/* Single DrQ kernels on device 0, null stream, host pointers in and out; 0 or a negative errno (-22
+ * for bad sizes or an unsupported channel pair, before anything is launched).  Every device output
+ * lies between two 256-byte bands of a fixed byte and starts as all-ones words (NaN as float): a
+ * written band returns -5 with the buffer named in mtsac_last_error, an element the kernel left
+ * alone comes back NaN.  Tests only.
+ *
+ * One 3x3 / stride 1 / SAME conv pass as the engine launches it (NHWC, kernel [3][3][ci][co]):
+ *   kind 0 forward: x input, flags bit 0 relu_in, aux residual (nullable), w2 / bias2 (nullable) the
+ *     second parameter set of images [B1, B), out [B][H][W][co];
+ *   kind 1 data gradient: x dout, aux mask (nullable), aux2 dres (nullable), out din [B][H][W][ci];
+ *   kind 2 weight gradient: x input, aux dout, flags bit 0 relu_in, out dw [3][3][ci][co], out2 db [co];
+ *     flags bit 1: the partials are left (defer_sum) and reduced by the one-segment form of the
+ *     update's partial-sum launch. */
+int mtsac_debug_drq_conv(int kind, int flags, int B, int B1, int H, int W, int ci, int co, const float* x,
+                         const float* w, const float* bias, const float* w2, const float* bias2, const float* aux,
+                         const float* aux2, float* out, float* out2);
+/* What the conv launcher of `kind` runs at this shape under the current masks: out[0] family
+ * (0 one lane per pixel / im2col, 1 row tiles, 2 split2h MFMA, 3 f32 MFMA), out[1] rows per tile,
+ * out[2] tiles per image (0 when not tiled), out[3] grid blocks.  The launchers decide through the
+ * same functions. */
+int mtsac_debug_drq_conv_path(int kind, int B, int H, int W, int ci, int co, int* out);
+/* Max pool 3x3 / stride 2 / SAME forward then backward: out, arg [B][Ho][Wo][C] (argmax tap 0..8),
+ * din [B][H][W][C] from dout [B][Ho][Wo][C]; C a multiple of 4. */
+int mtsac_debug_drq_maxpool(int B, int H, int W, int C, const float* in, float* out, unsigned char* arg,
+                            const float* dout, float* din);
+/* The C51 trio on head outputs hc_* [B][ldh] = [adv (A Z) | val (Z)] before the biases hb_* [(A + 1) Z],
+ * ldh >= (A + 1) Z: the target m [B][Z] and a_next [B] from (hc_n online, hc_t target), q [B][A] of
+ * hc_n, then the loss at act from hc_s and m: dh [B][ldh] (columns past (A + 1) Z untouched),
+ * loss_b [B], logit_b [B]. */
+int mtsac_debug_drq_c51(int B, int A, int Z, int ldh, const float* hc_s, const float* hc_n, const float* hc_t,
+                        const float* hb_on, const float* hb_tg, const float* rew, const float* done, const int* act,
+                        float gamma_n, float vmin, float vmax, float* m, int* a_next, float* q, float* dh,
+                        float* loss_b, float* logit_b);
+
 /* Eager update_many overlaps consecutive steps (the next gather and critic(s, a) forward beside
  * the previous actor backward / all-reduce / Adam): on = 1 always, 0 never (whole steps), -1 the
  * default (when the trunk gradients go through a device collective: RCCL or the modelled one).

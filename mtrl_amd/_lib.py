@@ -166,6 +166,10 @@ SIGNATURES = {
     "mtsac_debug_drq_legacy": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_drq_wgrad_blocks": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_drq_conv_bench": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double)]),
+    "mtsac_debug_drq_conv": (ctypes.c_int, [ctypes.c_int] * 8 + [P] * 9),
+    "mtsac_debug_drq_conv_path": (ctypes.c_int, [ctypes.c_int] * 6 + [P]),
+    "mtsac_debug_drq_maxpool": (ctypes.c_int, [ctypes.c_int] * 4 + [P] * 5),
+    "mtsac_debug_drq_c51": (ctypes.c_int, [ctypes.c_int] * 4 + [P] * 8 + [ctypes.c_float] * 3 + [P] * 6),
     "mtsac_debug_set_pipeline": (ctypes.c_int, [P, I32]),
     "mtsac_debug_lane_mode": (ctypes.c_int, [P]),
     "mtsac_debug_check_guards": (ctypes.c_int, [P]),

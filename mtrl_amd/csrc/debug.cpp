@@ -1,6 +1,7 @@
 // debug.cpp -- test-only entry points (include/mtsac_debug.h) for the plane GEMM.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -77,6 +78,70 @@ __bf16* make_planes(DevBuf& db, const float* dsrc, int rows, int K, bool kmajor,
   __bf16* out = db.get<__bf16>(3 * ps);
   if (out) split_into(dsrc, rows, K, kmajor, out);
   return out;
+}
+
+// Device buffers of the single-kernel DrQ entry points.  An output lies between two 256-byte bands
+// of GUARD_BYTE and starts as all-ones words (NaN as float, -1 as int, 255 as byte), so a store
+// outside it and an element the kernel left alone both show; the bands only detect.
+constexpr size_t GUARD = 256;
+constexpr int GUARD_BYTE = 0xA5;
+struct Guarded {
+  DevBuf mem;
+  struct Out {
+    unsigned char* raw;
+    size_t bytes;
+    const char* name;
+  };
+  std::vector<Out> outs;
+  bool ok = true;
+  template <typename T>
+  T* in(const T* host, size_t n) {  // null host: no buffer
+    if (!host) return nullptr;
+    T* d = mem.get<T>(n);
+    if (!d || hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    return d;
+  }
+  template <typename T>
+  T* out(size_t n, const char* name) {
+    const size_t bytes = n * sizeof(T);
+    unsigned char* raw = mem.get<unsigned char>(bytes + 2 * GUARD);
+    if (!raw || hipMemset(raw, GUARD_BYTE, bytes + 2 * GUARD) != hipSuccess ||
+        hipMemset(raw + GUARD, 0xFF, bytes) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    outs.push_back({raw, bytes, name});
+    return reinterpret_cast<T*>(raw + GUARD);
+  }
+  // 0, or -5 with the first written band named in mtsac_last_error
+  int check() {
+    unsigned char band[2 * GUARD];
+    for (const Out& o : outs) {
+      if (hipMemcpy(band, o.raw, GUARD, hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(band + GUARD, o.raw + GUARD + o.bytes, GUARD, hipMemcpyDeviceToHost) != hipSuccess)
+        return -5;
+      for (size_t i = 0; i < 2 * GUARD; ++i)
+        if (band[i] != GUARD_BYTE) {
+          char msg[160];
+          snprintf(msg, sizeof msg, "guard band written: buffer %s, %s band, byte %d", o.name,
+                   i < GUARD ? "leading" : "trailing", (int)(i % GUARD));
+          set_last_error(msg);
+          return -5;
+        }
+    }
+    return 0;
+  }
+  template <typename T>
+  bool back(T* host, const T* dev, size_t n) {
+    return hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+  }
+};
+
+int sync_rc(const char* what) {
+  const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize();
+  if (e1 == hipSuccess && e2 == hipSuccess) return 0;
+  set_last_error((std::string(what) + ": " + hipGetErrorString(e1 != hipSuccess ? e1 : e2)).c_str());
+  return -5;
 }
 
 }  // namespace
@@ -501,6 +566,125 @@ int mtsac_debug_drq_conv_bench(int kind, int B, int H, int W, int ci, int co, in
   if (us < 0) return -12;
   *us_per_launch = us;
   return hipDeviceSynchronize() == hipSuccess ? 0 : -5;
+}
+
+// what the conv launcher of `kind` runs at this shape under the current masks (drq::conv_path)
+int mtsac_debug_drq_conv_path(int kind, int B, int H, int W, int ci, int co, int* out) {
+  if (kind < 0 || kind > 2 || B < 1 || H < 1 || W < 1 || !out || !drq::conv_supported(ci, co) ||
+      (long long)B * H * W * 16 >= (1LL << 31))
+    return -22;
+  const drq::ConvPath p = drq::conv_path(kind, B, H, W, ci, co);
+  out[0] = p.family;
+  out[1] = p.R;
+  out[2] = p.n;
+  out[3] = p.blocks;
+  return 0;
+}
+
+// one conv pass as the engine launches it, host pointers in and out (mtsac_debug.h)
+int mtsac_debug_drq_conv(int kind, int flags, int B, int B1, int H, int W, int ci, int co, const float* x,
+                         const float* w, const float* bias, const float* w2, const float* bias2, const float* aux,
+                         const float* aux2, float* out, float* out2) {
+  if (kind < 0 || kind > 2 || (flags & ~3) || B < 1 || H < 1 || W < 1 || !x || (kind != 2 && !w) || !out ||
+      !drq::conv_supported(ci, co) || (long long)B * H * W * 16 >= (1LL << 31))
+    return -22;
+  if (kind == 0 && (!bias || (w2 != nullptr) != (bias2 != nullptr) || (w2 && (B1 < 0 || B1 > B)) || (flags & 2)))
+    return -22;
+  if (kind == 1 && flags) return -22;
+  if (kind == 2 && (!aux || !out2)) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t np = (size_t)B * H * W, nw = (size_t)9 * ci * co;
+  Guarded g;
+  int rc = 0;
+  if (kind == 0) {
+    const float* dx = g.in(x, np * ci);
+    const float *dw = g.in(w, nw), *dbi = g.in(bias, (size_t)co), *dw2 = g.in(w2, nw), *db2 = g.in(bias2, (size_t)co);
+    const float* dres = g.in(aux, np * co);
+    float* dout = g.out<float>(np * co, "out");
+    if (!g.ok) return -12;
+    drq::conv_fwd(dx, dw, dbi, dres, dout, B, H, W, ci, co, (flags & 1) != 0, nullptr, dw2, db2, w2 ? B1 : -1);
+    if ((rc = sync_rc("conv_fwd")) || (rc = g.check())) return rc;
+    if (!g.back(out, dout, np * co)) return -5;
+  } else if (kind == 1) {
+    const float *ddout = g.in(x, np * co), *dw = g.in(w, nw), *dmask = g.in(aux, np * ci), *ddres = g.in(aux2, np * ci);
+    float* ddin = g.out<float>(np * ci, "din");
+    if (!g.ok) return -12;
+    drq::conv_bwd_data(ddout, dw, dmask, ddres, ddin, B, H, W, ci, co, nullptr);
+    if ((rc = sync_rc("conv_bwd_data")) || (rc = g.check())) return rc;
+    if (!g.back(out, ddin, np * ci)) return -5;
+  } else {
+    const int G = drq::conv_wgrad_blocks(B, H, W, ci, co), n = (int)nw + co;
+    const bool defer = (flags & 2) != 0;
+    const float *dx = g.in(x, np * ci), *ddout = g.in(aux, np * co);
+    float* part = g.out<float>((size_t)G * n, "part");
+    float* ddw = g.out<float>(nw, "dw");
+    float* ddb = g.out<float>((size_t)co, "db");
+    if (!g.ok) return -12;
+    const drq::SumSeg seg{part, ddw, ddb, G, n, (int)nw, 0};
+    const drq::SumSeg* dseg = g.in(&seg, 1);
+    if (!g.ok) return -12;
+    drq::conv_wgrad(dx, ddout, part, ddw, ddb, B, H, W, ci, co, (flags & 1) != 0, nullptr, defer);
+    if (defer) drq::sum_parts_multi(dseg, 1, drq::sum_parts_blocks(ci, co), nullptr);
+    if ((rc = sync_rc("conv_wgrad")) || (rc = g.check())) return rc;
+    if (!g.back(out, ddw, nw) || !g.back(out2, ddb, (size_t)co)) return -5;
+  }
+  return 0;
+}
+
+// maxpool_fwd then maxpool_bwd (3 x 3 / stride 2 / SAME, NHWC): out, arg [B][Ho][Wo][C], din [B][H][W][C]
+int mtsac_debug_drq_maxpool(int B, int H, int W, int C, const float* in, float* out, unsigned char* arg,
+                            const float* dout, float* din) {
+  if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 || !in || !out || !arg || !dout || !din ||
+      (long long)B * H * W * C >= (1LL << 31))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t ni = (size_t)B * H * W * C, no = (size_t)B * ((H + 1) / 2) * ((W + 1) / 2) * C;
+  Guarded g;
+  const float *d_in = g.in(in, ni), *d_dout = g.in(dout, no);
+  float* d_out = g.out<float>(no, "out");
+  unsigned char* d_arg = g.out<unsigned char>(no, "arg");
+  float* d_din = g.out<float>(ni, "din");
+  if (!g.ok) return -12;
+  drq::maxpool_fwd(d_in, d_out, d_arg, B, H, W, C, nullptr);
+  drq::maxpool_bwd(d_dout, d_arg, d_din, B, H, W, C, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("maxpool")) || (rc = g.check())) return rc;
+  return g.back(out, d_out, no) && g.back(arg, d_arg, no) && g.back(din, d_din, ni) ? 0 : -5;
+}
+
+// c51_target(hc_n, hc_t) -> m, a_next; q_values(hc_n) -> q; c51_loss(hc_s, m) -> dh, loss_b, logit_b
+int mtsac_debug_drq_c51(int B, int A, int Z, int ldh, const float* hc_s, const float* hc_n, const float* hc_t,
+                        const float* hb_on, const float* hb_tg, const float* rew, const float* done, const int* act,
+                        float gamma_n, float vmin, float vmax, float* m, int* a_next, float* q, float* dh,
+                        float* loss_b, float* logit_b) {
+  if (B < 1 || A < 1 || Z < 2 || Z > 64 || ldh < (A + 1) * Z || !(vmax > vmin) || !hc_s || !hc_n || !hc_t || !hb_on ||
+      !hb_tg || !rew || !done || !act || !m || !a_next || !q || !dh || !loss_b || !logit_b ||
+      (long long)B * ldh >= (1LL << 31))
+    return -22;
+  for (int b = 0; b < B; ++b)
+    if (act[b] < 0 || act[b] >= A) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t nh = (size_t)B * ldh, nb = (size_t)(A + 1) * Z;
+  Guarded g;
+  const float *d_s = g.in(hc_s, nh), *d_n = g.in(hc_n, nh), *d_t = g.in(hc_t, nh);
+  const float *d_bon = g.in(hb_on, nb), *d_btg = g.in(hb_tg, nb), *d_rew = g.in(rew, (size_t)B), *d_done = g.in(done, (size_t)B);
+  const int* d_act = g.in(act, (size_t)B);
+  float* d_m = g.out<float>((size_t)B * Z, "m");
+  int* d_an = g.out<int>((size_t)B, "a_next");
+  float* d_q = g.out<float>((size_t)B * A, "q");
+  float* d_dh = g.out<float>(nh, "dh");
+  float* d_lb = g.out<float>((size_t)B, "loss_b");
+  float* d_gb = g.out<float>((size_t)B, "logit_b");
+  if (!g.ok) return -12;
+  drq::c51_target(d_n, d_t, ldh, d_bon, d_btg, A, Z, d_rew, d_done, gamma_n, vmin, vmax, d_m, d_an, B, nullptr);
+  drq::q_values(d_n, ldh, d_bon, A, Z, vmin, vmax, d_q, B, nullptr);
+  drq::c51_loss(d_s, ldh, d_bon, A, Z, d_act, d_m, d_dh, d_lb, d_gb, B, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("c51")) || (rc = g.check())) return rc;
+  return g.back(m, d_m, (size_t)B * Z) && g.back(a_next, d_an, (size_t)B) && g.back(q, d_q, (size_t)B * A) &&
+                 g.back(dh, d_dh, nh) && g.back(loss_b, d_lb, (size_t)B) && g.back(logit_b, d_gb, (size_t)B)
+             ? 0
+             : -5;
 }
 
 }  // extern "C"

@@ -1109,7 +1109,8 @@ __global__ __launch_bounds__(256) void sum_parts_multi_kernel(const SumSeg* __re
 // first in row-major order on ties -- lax.reduce_window's max has no defined tie rule for the
 // gradient; jax's select-and-scatter takes the first maximum, as here)
 __global__ void maxpool_fwd_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                   unsigned char* __restrict__ arg, int B, int H, int W, int C, int Ho, int Wo, int lo) {
+                                   unsigned char* __restrict__ arg, int B, int H, int W, int C, int Ho, int Wo, int loy,
+                                   int lox) {
   // one lane per 4 channels of one output pixel: float4 loads / stores, 32-bit index math.  The nine
   // window loads are unconditional (clamped into the image, an outside tap then skipped), so they are
   // all in flight at once: under a branch each was waited for at the branch's end, one latency a tap
@@ -1125,14 +1126,14 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ in, float* __restri
   float4 v[9];
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    const int y = min(max(2 * oy - lo + tap / 3, 0), H - 1), x = min(max(2 * ox - lo + tap % 3, 0), W - 1);
+    const int y = min(max(2 * oy - loy + tap / 3, 0), H - 1), x = min(max(2 * ox - lox + tap % 3, 0), W - 1);
     v[tap] = *reinterpret_cast<const float4*>(in + ((b * H + y) * W + x) * C + c);
   }
   float4 best = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
   uchar4 bi = make_uchar4(0, 0, 0, 0);
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    const int y = 2 * oy - lo + tap / 3, x = 2 * ox - lo + tap % 3;
+    const int y = 2 * oy - loy + tap / 3, x = 2 * ox - lox + tap % 3;
     if (y < 0 || y >= H || x < 0 || x >= W) continue;
     const unsigned char t = (unsigned char)tap;
     if (v[tap].x > best.x) { best.x = v[tap].x; bi.x = t; }
@@ -1150,7 +1151,8 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ in, float* __restri
 // size 3); their four (arg, dout) pairs are loaded unconditionally at clamped addresses and added in
 // window order, skipping the windows that do not cover the pixel.
 __global__ void maxpool_bwd_kernel(const float* __restrict__ dout, const unsigned char* __restrict__ arg,
-                                   float* __restrict__ din, int B, int H, int W, int C, int Ho, int Wo, int lo) {
+                                   float* __restrict__ din, int B, int H, int W, int C, int Ho, int Wo, int loy,
+                                   int lox) {
   const int C4 = C >> 2;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * H * W * C4) return;
@@ -1161,8 +1163,8 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ dout, const unsigne
   const int y = r % H;
   const int b = r / H;
   // windows o with 2 o - lo <= y <= 2 o - lo + 2, in order
-  const int oy0 = y + lo - 2 <= 0 ? 0 : (y + lo - 1) / 2, oy1 = min((y + lo) / 2, Ho - 1);
-  const int ox0 = x + lo - 2 <= 0 ? 0 : (x + lo - 1) / 2, ox1 = min((x + lo) / 2, Wo - 1);
+  const int oy0 = y + loy - 2 <= 0 ? 0 : (y + loy - 1) / 2, oy1 = min((y + loy) / 2, Ho - 1);
+  const int ox0 = x + lox - 2 <= 0 ? 0 : (x + lox - 1) / 2, ox1 = min((x + lox) / 2, Wo - 1);
   uchar4 a[2][2];
   float4 d[2][2];
 #pragma unroll
@@ -1176,11 +1178,11 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ dout, const unsigne
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
-    const int oy = oy0 + u, ty = y - (2 * oy - lo);
+    const int oy = oy0 + u, ty = y - (2 * oy - loy);
     if (oy > oy1 || ty < 0 || ty > 2) continue;
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
-      const int ox = ox0 + v, tx = x - (2 * ox - lo);
+      const int ox = ox0 + v, tx = x - (2 * ox - lox);
       if (ox > ox1 || tx < 0 || tx > 2) continue;
       const unsigned char t = (unsigned char)(ty * 3 + tx);
       if (a[u][v].x == t) s.x += d[u][v].x;
@@ -1532,24 +1534,31 @@ __global__ void enc_grad_kernel(const float* __restrict__ dfeat, int ldf, const 
 
 // ------------------------------------------------------------------ AdamW + Polyak + norms
 // optax.adamw (weight decay on every leaf, no clip); target = tau p + (1 - tau) target;
-// sumsq partials of g and of the PRE-update p (the logged norms)
+// sumsq partials of g and of the PRE-update p (the logged norms).  The element update runs in double
+// from the float32 operands and constants, each stored value rounded once: mu' = (1 - b1) g + b1 mu is
+// a sum whose terms nearly cancel on some elements once mu is non-zero, where a float32 sum is off by
+// 2^-23 of the |terms| -- 6e-4 of the result on the worst of 1e5 elements -- and that error went
+// straight into the step of parameters near zero.  bc1, bc2: the bias corrections 1 - b^count, formed
+// in double on the host (1 - powf(0.999f, 2) carries 1.5e-5 of relative error in float32).  The
+// kernel streams nine arrays; the double arithmetic is hidden behind them.
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ mu,
                                                     float* __restrict__ nu, const float* __restrict__ g,
                                                     float* __restrict__ tgt, long long n, float lr, float b1,
-                                                    float b2, float eps, float wd, float tau, int count,
-                                                    float* __restrict__ part) {
-  const float bc1 = 1.0f - powf(b1, (float)count), bc2 = 1.0f - powf(b2, (float)count);
+                                                    float b2, float eps, float wd, float tau, double bc1,
+                                                    double bc2, float* __restrict__ part) {
+  const double c1 = (double)(1.0f - b1), c2 = (double)(1.0f - b2);  // the float32 constants, as optax holds them
   float sg = 0.f, sp = 0.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     const float gi = g[i], pi = p[i];
     sg += gi * gi;
     sp += pi * pi;
-    const float m = (1.0f - b1) * gi + b1 * mu[i];
-    const float v = (1.0f - b2) * (gi * gi) + b2 * nu[i];
-    mu[i] = m;
-    nu[i] = v;
-    const float u = (m / bc1) / (sqrtf(v / bc2) + eps) + wd * pi;
-    const float np = pi + (-lr) * u;
+    const double gd = (double)gi, pd = (double)pi;
+    const double m = c1 * gd + (double)b1 * (double)mu[i];
+    const double v = c2 * (gd * gd) + (double)b2 * (double)nu[i];
+    mu[i] = (float)m;
+    nu[i] = (float)v;
+    const double u = (m / bc1) / (sqrt(v / bc2) + (double)eps) + (double)wd * pd;
+    const float np = (float)(pd - (double)lr * u);
     p[i] = np;
     tgt[i] = tau * np + (1.0f - tau) * tgt[i];
   }
@@ -1857,19 +1866,90 @@ static bool conv_h2_on(const ConvGeo& g, int KI, int bit) {
   return g.R > 0 && shape && !(g_drq_legacy & 16) && !(g_drq_legacy & bit) && !(g_drq_mfma & bit);
 }
 
+// What a forward / data-gradient launcher runs under the current masks, decided in one place (the
+// launchers and mtsac_debug_drq_conv_path both ask here): family 0 one lane per pixel, 1 row tiles,
+// 2 split2h MFMA, 3 f32 MFMA; geo / ng of the tiled families, G channels per lane of the pixel
+// kernels, the grid (gx, gy)
+struct ConvSel {
+  int family, ng, G;
+  ConvGeo geo;
+  unsigned gx, gy;
+};
+static ConvSel conv_fwd_sel(int B, int B1, int H, int W, int ci, int co) {
+  ConvSel s{};
+  s.gy = 1;
+  const long long npix = (long long)B * H * W, n1 = (long long)B1 * H * W;
+  if (ci >= 8 && g_drq_fwd_g == 0) {
+    s.geo = conv_h2_geo(H, W, ci);
+    if (conv_h2_on(s.geo, ci, 1)) {
+      s.family = 2;
+      s.gx = (unsigned)(B * s.geo.n);
+      return s;
+    }
+  }
+  s.geo = conv_geo(H, W, ci, co, &s.ng);
+  if (conv_rows_on(s.ng, g_drq_fwd_g, 1)) {
+    s.family = 1;
+    s.gx = (unsigned)(B * s.geo.n);
+    return s;
+  }
+  if (g_drq_mfma & 1) {
+    constexpr int PB = 64 * MFMA_TW;
+    s.family = 3;
+    s.gx = (unsigned)((n1 + PB - 1) / PB + (npix - n1 + PB - 1) / PB);
+    return s;
+  }
+  s.G = conv_fwd_group(co, npix);
+  s.gx = blocks(n1) + blocks(npix - n1);
+  s.gy = (unsigned)(co / s.G);
+  return s;
+}
+static ConvSel conv_bwd_sel(int B, int H, int W, int ci, int co) {
+  ConvSel s{};
+  s.gy = 1;
+  const long long npix = (long long)B * H * W;
+  if (co >= 8 && g_drq_bwd_g == 0) {  // the transposed conv on split2h MFMA: KI = co, KO = ci
+    s.geo = conv_h2_geo(H, W, co);
+    if (conv_h2_on(s.geo, co, 2)) {
+      s.family = 2;
+      s.gx = (unsigned)(B * s.geo.n);
+      return s;
+    }
+  }
+  s.geo = conv_geo(H, W, co, ci, &s.ng);
+  // measured (profiles/r6o_drq/conv_bench.txt): the row-tile data grad wins with 16 dout channels
+  // from 21 x 21 up (21 x 21: 13.6 vs 28.2 us, 42 x 42 8 -> 16: 25.0 vs 27.9) and loses with 8 (42 x 42:
+  // 15.2 vs 13.9) and at 11 x 11 (8.5 vs 7.9): it runs for co = 16, W >= 16
+  if (((co >= 16 && W >= 16) || (g_drq_legacy & 8)) && conv_rows_on(s.ng, g_drq_bwd_g, 2)) {
+    s.family = 1;
+    s.gx = (unsigned)(B * s.geo.n);
+    return s;
+  }
+  if (g_drq_mfma & 2) {
+    constexpr int PB = 64 * MFMA_TW;
+    s.family = 3;
+    s.gx = (unsigned)((npix + PB - 1) / PB);
+    return s;
+  }
+  s.G = conv_bwd_group(ci);
+  s.gx = blocks(npix);
+  s.gy = (unsigned)(ci / s.G);
+  return s;
+}
+
 void conv_fwd(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
               int ci, int co, bool relu_in, hipStream_t st, const float* w2, const float* bias2, int B1) {
-  const long long npix = (long long)B * H * W;
-  const int G = conv_fwd_group(co, npix);
   if (w2 == nullptr || B1 < 0 || B1 > B) {  // one parameter set
     w2 = w;
     bias2 = bias;
     B1 = B;
   }
-  if (ci >= 8 && g_drq_fwd_g == 0) {
-    const ConvGeo geo = conv_h2_geo(H, W, ci);
-    if (conv_h2_on(geo, ci, 1)) {
-      const dim3 gr((unsigned)(B * geo.n)), tb(256);
+  const ConvSel sel = conv_fwd_sel(B, B1, H, W, ci, co);
+  const ConvGeo geo = sel.geo;
+  const int G = sel.G, ng = sel.ng;
+  {
+    if (sel.family == 2) {
+      const dim3 gr(sel.gx), tb(256);
 #define C_FH(a, b)                                                                                                   \
   if (ci == a && co == b) {                                                                                          \
     if (relu_in && res) hipLaunchKernelGGL((conv_h2_kernel<a, b, true, true, false, true>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
@@ -1883,10 +1963,8 @@ void conv_fwd(const float* in, const float* w, const float* bias, const float* r
     }
   }
   {
-    int ng = 0;
-    const ConvGeo geo = conv_geo(H, W, ci, co, &ng);
-    if (conv_rows_on(ng, g_drq_fwd_g, 1)) {
-      const dim3 gr((unsigned)(B * geo.n)), tb(256);
+    if (sel.family == 1) {
+      const dim3 gr(sel.gx), tb(256);
 #define C_FR_G(a, b, cg)                                                                                            \
   if (relu_in && res) hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, true, false, true>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
   else if (relu_in) hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, true, false, false>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
@@ -1904,10 +1982,8 @@ void conv_fwd(const float* in, const float* w, const float* bias, const float* r
 #undef C_FR_G
     }
   }
-  if (g_drq_mfma & 1) {
-    constexpr int PB = 64 * MFMA_TW;
-    const long long n1 = (long long)B1 * H * W;
-    const dim3 gm((unsigned)((n1 + PB - 1) / PB + (npix - n1 + PB - 1) / PB)), tm(256);
+  if (sel.family == 3) {
+    const dim3 gm(sel.gx), tm(256);
 #define C_FWDM(a, b)                                                                                                 \
   if (ci == a && co == b) {                                                                                          \
     if (relu_in && res) hipLaunchKernelGGL((conv_mfma_kernel<a, b, true, true, true, MFMA_TW>), gm, tm, 0, st, in, w, bias, w2, bias2, nullptr, res, out, B, B1, H, W); \
@@ -1919,8 +1995,7 @@ void conv_fwd(const float* in, const float* w, const float* bias, const float* r
     CONV_CASES(C_FWDM)
 #undef C_FWDM
   }
-  const long long n1 = (long long)B1 * H * W;
-  const dim3 g(blocks(n1) + blocks(npix - n1), co / G), t(256);
+  const dim3 g(sel.gx, sel.gy), t(256);
 #define C_FWD_G(a, b, cg)                                                                                           \
   if (relu_in && res) hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, true, true>), g, t, 0, st, in, w, bias, w2, bias2, res, out, B, B1, H, W); \
   else if (relu_in) hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, true, false>), g, t, 0, st, in, w, bias, w2, bias2, res, out, B, B1, H, W); \
@@ -1940,11 +2015,12 @@ void conv_fwd(const float* in, const float* w, const float* bias, const float* r
 
 void conv_bwd_data(const float* dout, const float* w, const float* mask, const float* dres, float* din, int B, int H,
                    int W, int ci, int co, hipStream_t st) {
-  const long long npix = (long long)B * H * W;
-  if (co >= 8 && g_drq_bwd_g == 0) {  // the transposed conv on split2h MFMA: KI = co, KO = ci
-    const ConvGeo geo = conv_h2_geo(H, W, co);
-    if (conv_h2_on(geo, co, 2)) {
-      const dim3 gr((unsigned)(B * geo.n)), tb(256);
+  const ConvSel sel = conv_bwd_sel(B, H, W, ci, co);
+  const ConvGeo geo = sel.geo;
+  const int G = sel.G, ng = sel.ng;
+  {  // the transposed conv on split2h MFMA: KI = co, KO = ci
+    if (sel.family == 2) {
+      const dim3 gr(sel.gx), tb(256);
 #define C_BH(a, b)                                                                                                   \
   if (ci == a && co == b) {                                                                                          \
     if (mask && dres) hipLaunchKernelGGL((conv_h2_kernel<b, a, false, false, true, true>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
@@ -1958,13 +2034,8 @@ void conv_bwd_data(const float* dout, const float* w, const float* mask, const f
     }
   }
   {  // the transposed conv: KI = co (dout channels), KO = ci
-    int ng = 0;
-    const ConvGeo geo = conv_geo(H, W, co, ci, &ng);
-    // measured (profiles/r6o_drq/conv_bench.txt): the row-tile data grad wins with 16 dout channels
-    // from 21 x 21 up (21 x 21: 13.6 vs 28.2 us, 42 x 42 8 -> 16: 25.0 vs 27.9) and loses with 8 (42 x 42:
-    // 15.2 vs 13.9) and at 11 x 11 (8.5 vs 7.9): it runs for co = 16, W >= 16
-    if (((co >= 16 && W >= 16) || (g_drq_legacy & 8)) && conv_rows_on(ng, g_drq_bwd_g, 2)) {
-      const dim3 gr((unsigned)(B * geo.n)), tb(256);
+    if (sel.family == 1) {
+      const dim3 gr(sel.gx), tb(256);
 #define C_BR_G(a, b, cg)                                                                                            \
   if (mask && dres) hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, true, true>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
   else if (mask) hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, true, false>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
@@ -1984,9 +2055,8 @@ void conv_bwd_data(const float* dout, const float* w, const float* mask, const f
 #undef C_BR_G
     }
   }
-  if (g_drq_mfma & 2) {  // K channels = co, N = ci
-    constexpr int PB = 64 * MFMA_TW;
-    const dim3 gm((unsigned)((npix + PB - 1) / PB)), tm(256);
+  if (sel.family == 3) {  // K channels = co, N = ci
+    const dim3 gm(sel.gx), tm(256);
 #define C_BDM(a, b)                                                                                                  \
   if (ci == a && co == b) {                                                                                          \
     if (dres) hipLaunchKernelGGL((conv_mfma_kernel<b, a, false, false, true, MFMA_TW>), gm, tm, 0, st, dout, w, nullptr, w, nullptr, mask, dres, din, B, B, H, W); \
@@ -1996,8 +2066,7 @@ void conv_bwd_data(const float* dout, const float* w, const float* mask, const f
     CONV_CASES(C_BDM)
 #undef C_BDM
   }
-  const int G = conv_bwd_group(ci);
-  const dim3 g(blocks(npix), ci / G), t(256);
+  const dim3 g(sel.gx, sel.gy), t(256);
 #define C_BD_G(a, b, cg)                                                                                            \
   if (mask && dres) hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, true, true>), g, t, 0, st, dout, w, mask, dres, din, B, H, W); \
   else if (mask) hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, true, false>), g, t, 0, st, dout, w, mask, dres, din, B, H, W); \
@@ -2064,19 +2133,44 @@ int conv_wgrad_blocks(int B, int H, int W, int ci, int co) {
   return (int)std::min<long long>(2048, std::max<long long>(1, (npix + 63) / 64));
 }
 
+// the weight-grad launcher's choice (family 0 im2col, 1 row tiles, 3 f32 MFMA) and its G blocks
+struct WgSel {
+  int family, G;
+  WgGeo geo;
+};
+static WgSel conv_wgrad_sel(int B, int H, int W, int ci, int co) {
+  WgSel s{};
+  s.geo = wgrad_geo(B, H, W, ci, co);
+  s.G = conv_wgrad_blocks(B, H, W, ci, co);
+  s.family = wgrad_rows(s.geo) ? 1 : (g_drq_mfma & 4) ? 3 : 0;
+  return s;
+}
+
+ConvPath conv_path(int kind, int B, int H, int W, int ci, int co) {
+  if (kind == 2) {
+    const WgSel s = conv_wgrad_sel(B, H, W, ci, co);
+    if (s.family == 1) return ConvPath{1, s.geo.R, s.geo.tiles / B, s.G};
+    return ConvPath{s.family, 0, 0, s.G};
+  }
+  const ConvSel s = kind == 0 ? conv_fwd_sel(B, B, H, W, ci, co) : conv_bwd_sel(B, H, W, ci, co);
+  const bool tiled = s.family == 1 || s.family == 2;
+  return ConvPath{s.family, tiled ? s.geo.R : 0, tiled ? s.geo.n : 0, (int)(s.gx * s.gy)};
+}
+
 void conv_wgrad(const float* in, const float* dout, float* part, float* dw, float* db, int B, int H, int W, int ci,
                 int co, bool relu_in, hipStream_t st, bool defer_sum) {
   const long long npix = (long long)B * H * W;
-  const WgGeo geo = wgrad_geo(B, H, W, ci, co);
-  const bool rows = wgrad_rows(geo);
-  const int G = conv_wgrad_blocks(B, H, W, ci, co);
+  const WgSel sel = conv_wgrad_sel(B, H, W, ci, co);
+  const WgGeo geo = sel.geo;
+  const bool rows = sel.family == 1;
+  const int G = sel.G;
   const int chunk = (int)(((npix + G - 1) / G + 15) / 16 * 16);
 #define C_WG(a, b)                                                                                             \
   if (ci == a && co == b) {                                                                                    \
     if (rows) {                                                                                                \
       if (relu_in) hipLaunchKernelGGL((conv_wgrad_rows_kernel<a, b, true>), dim3(G), dim3(256), 0, st, in, dout, part, geo); \
       else hipLaunchKernelGGL((conv_wgrad_rows_kernel<a, b, false>), dim3(G), dim3(256), 0, st, in, dout, part, geo);      \
-    } else if (g_drq_mfma & 4) {                                                                               \
+    } else if (sel.family == 3) {                                                                              \
       if (relu_in) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<a, b, true>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W, chunk); \
       else hipLaunchKernelGGL((conv_wgrad_mfma_kernel<a, b, false>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W, chunk);      \
     } else if (relu_in) hipLaunchKernelGGL((conv_wgrad_kernel<a, b, true>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W); \
@@ -2140,18 +2234,22 @@ void sum_parts_multi(const SumSeg* segs, int nseg, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(sum_parts_multi_kernel, dim3(blocks), dim3(256), 0, st, segs, nseg);
 }
 
+// SAME padding before the first row / column: half of the total, per axis (an even and an odd
+// extent pad differently: 4 x 5 takes 0 rows and 1 column)
+static int pool_lo(int n, int no) { return std::max((no - 1) * 2 + 3 - n, 0) / 2; }
+
 void maxpool_fwd(const float* in, float* out, unsigned char* arg, int B, int H, int W, int C, hipStream_t st) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-  const int lo = std::max((Ho - 1) * 2 + 3 - H, 0) / 2;
+  const int loy = pool_lo(H, Ho), lox = pool_lo(W, Wo);
   const long long n = (long long)B * Ho * Wo * (C / 4);  // C % 4 == 0, B H W C < 2^31 (drq_create)
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, in, out, arg, B, H, W, C, Ho, Wo, lo);
+  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(blocks(n)), dim3(256), 0, st, in, out, arg, B, H, W, C, Ho, Wo, loy, lox);
 }
 
 void maxpool_bwd(const float* dout, const unsigned char* arg, float* din, int B, int H, int W, int C, hipStream_t st) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-  const int lo = std::max((Ho - 1) * 2 + 3 - H, 0) / 2;
+  const int loy = pool_lo(H, Ho), lox = pool_lo(W, Wo);
   const long long n = (long long)B * H * W * (C / 4);
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(blocks(n)), dim3(256), 0, st, dout, arg, din, B, H, W, C, Ho, Wo, lo);
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(blocks(n)), dim3(256), 0, st, dout, arg, din, B, H, W, C, Ho, Wo, loy, lox);
 }
 
 void concat_feat(const float* enc, int nenc, const float* emb, int D, const int* task, int r0, int tmod, float* feat,
@@ -2220,7 +2318,8 @@ void enc_grad(const float* dfeat, int ldf, const float* enc, int nenc, float* de
 int adamw(float* p, float* mu, float* nu, const float* g, float* tgt, long long n, float lr, float b1, float b2,
           float eps, float wd, float tau, int count, float* part, int max_blocks, hipStream_t st) {
   const int G = (int)std::min<long long>(max_blocks, std::max<long long>(1, (n + 255) / 256));
-  hipLaunchKernelGGL(adamw_kernel, dim3(G), dim3(256), 0, st, p, mu, nu, g, tgt, n, lr, b1, b2, eps, wd, tau, count,
+  const double bc1 = 1.0 - std::pow((double)b1, (double)count), bc2 = 1.0 - std::pow((double)b2, (double)count);
+  hipLaunchKernelGGL(adamw_kernel, dim3(G), dim3(256), 0, st, p, mu, nu, g, tgt, n, lr, b1, b2, eps, wd, tau, bc1, bc2,
                      part);
   return G;
 }

@@ -66,6 +66,14 @@ struct ConvGeo {
 // defer_sum: leave the partials for one sum_parts_multi launch over every conv of the backward
 void conv_wgrad(const float* in, const float* dout, float* part, float* dw, float* db, int B, int H, int W, int ci,
                 int co, bool relu_in, hipStream_t st, bool defer_sum = false);
+// what a conv launcher runs under the current masks (kind 0 forward, 1 data grad, 2 weight grad;
+// the launchers decide through the same functions): family 0 one lane per pixel / im2col, 1 row
+// tiles, 2 split2h MFMA, 3 f32 MFMA; R rows per tile and n tiles per image (0 when not tiled);
+// grid blocks
+struct ConvPath {
+  int family, R, n, blocks;
+};
+ConvPath conv_path(int kind, int B, int H, int W, int ci, int co);
 // one conv's partial sums: part[G][n] -> dw[0, nw), db[0, n - nw); blocks [blk0, blk0 + sum_parts_blocks)
 struct SumSeg {
   const float* part;

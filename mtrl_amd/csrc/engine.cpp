@@ -42,6 +42,12 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+}  // namespace
+namespace mtsac {
+void set_last_error(const char* msg) { g_last_error = msg; }  // debug.cpp's entry points
+}  // namespace mtsac
+namespace {
+
 #define HIP_TRY(expr)                                                                      \
   do {                                                                                     \
     hipError_t _e = (expr);                                                                \

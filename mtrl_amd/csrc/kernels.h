@@ -634,4 +634,8 @@ void task_combine(const float* M, const float* w, int T, long long P, const Pcgr
 void pcgrad_logs(const float* solve_critic, const float* solve_actor, const float* row_explore, int B, float* logs,
                  hipStream_t st);
 
+// sets what mtsac_last_error returns on this thread (engine.cpp; the debug entry points name a
+// written guard band through it)
+void set_last_error(const char* msg);
+
 }  // namespace mtsac

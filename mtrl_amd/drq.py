@@ -88,6 +88,85 @@ def unbalanced_rows(rng: np.random.Generator, num_tasks: int, batch: int, pos: i
     return slots, tasks
 
 
+# ---- single kernels (include/mtsac_debug.h): numpy in, numpy out, on device 0.  Tests only.
+def _dbg_check(rc: int) -> int:
+    if rc < 0:
+        msg = L.load().mtsac_last_error()
+        raise L.MTSACError(f"libmtsac debug error {rc}: {msg.decode() if msg else ''}")
+    return rc
+
+
+def _f32(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+def debug_conv_path(kind: int, B: int, H: int, W: int, ci: int, co: int) -> tuple:
+    """(family, rows per tile, tiles per image, grid blocks) of the conv launcher under the current
+    masks: family 0 one lane per pixel / im2col, 1 row tiles, 2 split2h MFMA, 3 f32 MFMA."""
+    out = np.zeros(4, np.int32)
+    _dbg_check(L.load().mtsac_debug_drq_conv_path(kind, B, H, W, ci, co, _ptr(out)))
+    return tuple(int(v) for v in out)
+
+
+def debug_conv_fwd(x, w, bias, relu_in=False, res=None, w2=None, bias2=None, B1=-1) -> np.ndarray:
+    """x [B][H][W][ci], w [3][3][ci][co] -> [B][H][W][co]; images [B1, B) use (w2, bias2)."""
+    x, w, bias, res, w2, bias2 = (_f32(a) for a in (x, w, bias, res, w2, bias2))
+    B, H, W, ci = x.shape
+    co = w.shape[-1]
+    out = np.empty((B, H, W, co), np.float32)
+    _dbg_check(L.load().mtsac_debug_drq_conv(0, int(bool(relu_in)), B, B1, H, W, ci, co, _ptr(x), _ptr(w), _ptr(bias),
+                                             _ptr(w2), _ptr(bias2), _ptr(res), None, _ptr(out), None))
+    return out
+
+
+def debug_conv_bwd_data(dout, w, mask=None, dres=None) -> np.ndarray:
+    """dout [B][H][W][co], w [3][3][ci][co] -> din [B][H][W][ci] = conv^T(dout) [mask > 0] + dres."""
+    dout, w, mask, dres = (_f32(a) for a in (dout, w, mask, dres))
+    B, H, W, co = dout.shape
+    ci = w.shape[-2]
+    out = np.empty((B, H, W, ci), np.float32)
+    _dbg_check(L.load().mtsac_debug_drq_conv(1, 0, B, -1, H, W, ci, co, _ptr(dout), _ptr(w), None, None, None,
+                                             _ptr(mask), _ptr(dres), _ptr(out), None))
+    return out
+
+
+def debug_conv_wgrad(x, dout, relu_in=False, defer=False):
+    """x [B][H][W][ci], dout [B][H][W][co] -> (dw [3][3][ci][co], db [co]); defer: the partials are
+    reduced by the update's one-launch segment sum."""
+    x, dout = _f32(x), _f32(dout)
+    B, H, W, ci = x.shape
+    co = dout.shape[-1]
+    dw, db = np.empty((3, 3, ci, co), np.float32), np.empty(co, np.float32)
+    _dbg_check(L.load().mtsac_debug_drq_conv(2, int(bool(relu_in)) | (2 if defer else 0), B, -1, H, W, ci, co, _ptr(x),
+                                             None, None, None, None, _ptr(dout), None, _ptr(dw), _ptr(db)))
+    return dw, db
+
+
+def debug_maxpool(x, dout):
+    """x [B][H][W][C], dout [B][Ho][Wo][C] -> (out, arg uint8, din) of the 3x3 / 2 / SAME max pool."""
+    x, dout = _f32(x), _f32(dout)
+    B, H, W, C = x.shape
+    so = (B, (H + 1) // 2, (W + 1) // 2, C)
+    assert dout.shape == so, (dout.shape, so)
+    out, arg, din = np.empty(so, np.float32), np.empty(so, np.uint8), np.empty(x.shape, np.float32)
+    _dbg_check(L.load().mtsac_debug_drq_maxpool(B, H, W, C, _ptr(x), _ptr(out), _ptr(arg), _ptr(dout), _ptr(din)))
+    return out, arg, din
+
+
+def debug_c51(hc_s, hc_n, hc_t, hb_on, hb_tg, rew, done, act, A, Z, gamma_n, vmin, vmax):
+    """The C51 trio on head outputs [B][ldh] (before the biases hb [(A + 1) Z]): returns
+    (m [B][Z], a_next [B], q [B][A], dh [B][ldh], loss_b [B], logit_b [B])."""
+    hc_s, hc_n, hc_t, hb_on, hb_tg, rew, done = (_f32(a) for a in (hc_s, hc_n, hc_t, hb_on, hb_tg, rew, done))
+    act = np.ascontiguousarray(act, np.int32)
+    B, ldh = hc_s.shape
+    m, a_next, q = np.empty((B, Z), np.float32), np.empty(B, np.int32), np.empty((B, A), np.float32)
+    dh, loss_b, logit_b = np.empty((B, ldh), np.float32), np.empty(B, np.float32), np.empty(B, np.float32)
+    _dbg_check(L.load().mtsac_debug_drq_c51(B, A, Z, ldh, _ptr(hc_s), _ptr(hc_n), _ptr(hc_t), _ptr(hb_on), _ptr(hb_tg),
+                                            _ptr(rew), _ptr(done), _ptr(act), gamma_n, vmin, vmax, _ptr(m),
+                                            _ptr(a_next), _ptr(q), _ptr(dh), _ptr(loss_b), _ptr(logit_b)))
+    return m, a_next, q, dh, loss_b, logit_b
+
+
 class DrQEngine:
     def __init__(self, s: DrQSettings = DrQSettings(), device: int = 0):
         self.lib = L.load()

@@ -206,20 +206,33 @@ def forward(p: dict, x: torch.Tensor, task_ids: torch.Tensor, cfg: DrQConfig) ->
 def c51_target(logits_next_online, logits_next_target, rewards, dones, cfg: DrQConfig):
     """m of drqeps.py:273-298: argmax_a of the online expected Q at s', the target net's
     distribution at that action, projected onto the support (the l == u case drops its mass, as
-    the reference's two scatter-adds do)."""
-    B = logits_next_online.shape[0]
-    support = torch.linspace(cfg.v_min, cfg.v_max, cfg.n_atoms, dtype=logits_next_online.dtype)
+    the reference's two scatter-adds do).
+
+    The projection is discontinuous where b is integral, and the reference decides floor / ceil on
+    float32 arrays, so that part -- support, tz, b, floor, ceil -- is taken in float32 here too, in
+    the reference's order (delta_z and gamma ** nstep are Python doubles that meet the arrays as
+    weakly typed scalars: rounded once to float32).  In float64 a clamped top atom is exactly
+    integral at every atom count, where float32 gives e.g. 62.999996 at 64 atoms and keeps the mass.
+    A scatter target past the last atom (u = 62 at 62 atoms) is dropped, as jax's .at[].add does."""
+    B, Z = logits_next_online.shape[0], cfg.n_atoms
+    dt = logits_next_online.dtype
+    support = torch.linspace(cfg.v_min, cfg.v_max, Z, dtype=dt)
     q_next = (torch.softmax(logits_next_online, -1) * support).sum(-1)
     a_next = q_next.argmax(-1)
     target_dist = torch.softmax(logits_next_target, -1)[torch.arange(B), a_next]
-    tz = torch.clamp(rewards[:, None] + (cfg.gamma ** cfg.nstep) * (1 - dones[:, None]) * support, cfg.v_min, cfg.v_max)
-    dz = (cfg.v_max - cfg.v_min) / (cfg.n_atoms - 1)
-    b = (tz - cfg.v_min) / dz
-    l, u = torch.floor(b).long(), torch.ceil(b).long()
-    m = torch.zeros(B, cfg.n_atoms, dtype=b.dtype)
-    m.scatter_add_(1, l, target_dist * (u.to(b.dtype) - b))
-    m.scatter_add_(1, u, target_dist * (b - l.to(b.dtype)))
-    return m, a_next
+    f32 = torch.float32
+    dz = torch.tensor((cfg.v_max - cfg.v_min) / (Z - 1), dtype=f32)
+    vmin, vmax = torch.tensor(cfg.v_min, dtype=f32), torch.tensor(cfg.v_max, dtype=f32)
+    sup32 = vmin + torch.arange(Z, dtype=f32) * dz
+    gn = torch.tensor(cfg.gamma ** cfg.nstep, dtype=f32)
+    tz = torch.clamp(rewards.to(f32)[:, None] + (gn * (1 - dones.to(f32)[:, None])) * sup32, vmin, vmax)
+    b32 = (tz - vmin) / dz
+    l, u = torch.floor(b32).long(), torch.ceil(b32).long()
+    b = b32.to(dt)
+    m = torch.zeros(B, Z + 1, dtype=dt)  # column Z collects what falls past the last atom
+    m.scatter_add_(1, l.clamp(max=Z), target_dist * (u.to(dt) - b))
+    m.scatter_add_(1, u.clamp(max=Z), target_dist * (b - l.to(dt)))
+    return m[:, :Z].contiguous(), a_next
 
 
 def _ln_abs_back(a_dy, x, scale, eps):

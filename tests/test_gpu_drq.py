@@ -78,6 +78,12 @@ def test_update_matches_oracle(hw, hidden, B, mfma):
     (mtsac_debug_drq_mfma(7); measured slower, off by default) at the two smaller geometries -- at
     b256 their stack-0 Conv_0 bias error norm is 8x the PyTorch fp32 reference's (profiles/r4d_drq_tests.log),
     above this test's 4x bar though inside the elementwise floors."""
+    _check_update_matches_oracle(od.DrQConfig(hw=hw, n_hidden=hidden), B, hw + B, mfma)
+
+
+def _check_update_matches_oracle(cfg, B, seed, mfma=0):
+    """One update from zero moments against the float64 oracle: the logs, the gradient leaf by leaf,
+    the first AdamW step and the Polyak target."""
     import torch
 
     from mtrl_amd import _lib as L
@@ -85,8 +91,7 @@ def test_update_matches_oracle(hw, hidden, B, mfma):
     lib = L.load()
     old = lib.mtsac_debug_drq_mfma(mfma)
     try:
-        cfg = od.DrQConfig(hw=hw, n_hidden=hidden)
-        e, st, new, got, want, internals = _run_both(cfg, B, seed=hw + B)
+        e, st, new, got, want, internals = _run_both(cfg, B, seed=seed)
     finally:
         lib.mtsac_debug_drq_mfma(old)
     for k, v in want.items():
@@ -127,6 +132,113 @@ def test_update_matches_oracle(hw, hidden, B, mfma):
     dp_gpu, dp_ref = p - st.params, new.params - st.params
     assert np.median(np.abs(dp_gpu - dp_ref)) < 1e-7
     e.close()
+
+
+# (hw, hidden, B, A, Z, embed, tasks).  The feature row (encoder output + embedding) is read in
+# 16-byte chunks, so drq_create refuses a width that is no multiple of 4 (-95, with the reason):
+# 1 x 1 x 16 + 1 = 17 and 5 x 5 x 16 + 5 = 405 are asserted as refusals, and each geometry runs
+# with a 4-wide embedding instead.
+ODD_CONFIGS = [(4, 8, 3, 1, 2, 1, 1), (4, 8, 3, 1, 2, 4, 1), (10, 20, 9, 3, 33, 32, 2), (21, 36, 5, 7, 64, 64, 3),
+               (33, 64, 6, 18, 40, 5, 26), (33, 64, 6, 18, 40, 4, 26)]
+
+
+@pytest.mark.parametrize("hw,hidden,B,A,Z,embed,tasks", ODD_CONFIGS, ids=["x".join(map(str, c)) for c in ODD_CONFIGS])
+def test_update_matches_oracle_odd_configs(hw, hidden, B, A, Z, embed, tasks):
+    """test_update_matches_oracle's assertions away from the default head and the square 20 / 84
+    geometries: 1 x 1 feature maps (hw 4: the W < 2 conv paths), odd image sizes, 2 to 64 atoms,
+    one action, one task.  A configuration drq_create accepts must match the oracle."""
+    from mtrl_amd import _lib as L
+
+    cfg = od.DrQConfig(hw=hw, n_hidden=hidden, n_actions=A, n_atoms=Z, embed_dim=embed, num_tasks=tasks)
+    if (od.feat_dim(cfg) + embed) % 4:
+        with pytest.raises(L.MTSACError, match="-95.*multiples of 4"):
+            _engine(cfg, B)
+        return
+    _check_update_matches_oracle(cfg, B, hw + B)
+
+
+ADAM_COUNTS = [0, 1, 9, 100000]
+_adamw_runs = {}
+
+
+def _adamw_step(count):
+    """One update from non-zero moments at step `count` (hw 20, hidden 64, B 8) and float64
+    optax.adamw of the device's own gradient; the constants float32-rounded, as optax holds them on
+    float32 parameters.  Run once per count and shared by the tests below."""
+    from mtrl_amd import _lib as L
+
+    if count in _adamw_runs:
+        return _adamw_runs[count]
+    cfg = od.DrQConfig(hw=20, n_hidden=64)
+    B = 8
+    st = od.init_state(cfg, 21)
+    rng = np.random.default_rng(22)
+    f32 = lambda a: np.asarray(a, np.float32).astype(np.float64)
+    p0 = f32(st.params)
+    t0 = f32(p0 + rng.normal(0, 1e-3, p0.size))
+    mu0 = f32(1e-3 * rng.standard_normal(p0.size))
+    nu0 = f32(1e-6 * rng.random(p0.size) + 1e-12)
+    batch, aug = _batch(cfg, B, 23)
+    e = _engine(cfg, B)
+    e.set_params(L.DRQ_PARAMS, p0)
+    e.set_params(L.DRQ_TARGET, t0)
+    e.set_params(L.DRQ_ADAM_MU, mu0)
+    e.set_params(L.DRQ_ADAM_NU, nu0)
+    e.set_step(count)
+    e.update(batch, aug)
+    r = {"step": e.get_step(), "logs": e.logs(), "p0": p0, "g": e.get_params(L.DRQ_GRAD).astype(np.float64)}
+    for name, w in (("mu", L.DRQ_ADAM_MU), ("nu", L.DRQ_ADAM_NU), ("p", L.DRQ_PARAMS), ("tgt", L.DRQ_TARGET)):
+        r[name] = e.get_params(w).astype(np.float64)
+    e.close()
+    g = r["g"]
+    c = lambda v: float(np.float32(v))
+    b1, b2, lr, eps, wd, tau = (c(v) for v in (cfg.b1, cfg.b2, cfg.lr, cfg.eps, cfg.weight_decay, cfg.tau))
+    k = count + 1
+    c1, c2 = c(np.float32(1) - np.float32(cfg.b1)), c(np.float32(1) - np.float32(cfg.b2))
+    mu = c1 * g + b1 * mu0
+    nu = c2 * g * g + b2 * nu0
+    denom = (1 - b1 ** k) * (np.sqrt(nu / (1 - b2 ** k)) + eps)
+    r["mu_ref"], r["nu_ref"] = mu, nu
+    r["dp_ref"] = -lr * (mu / denom + wd * p0)
+    r["tgt_ref"] = tau * (p0 + r["dp_ref"]) + c(np.float32(1) - np.float32(cfg.tau)) * t0
+    r["dp"] = r["p"] - p0
+    r["step_bound"] = 2.0 ** -23 * np.abs(p0) + 1e-5 * np.abs(r["dp_ref"])
+    rel = lambda a, b: float((np.abs(a - b) / np.maximum(np.abs(b), 1e-300)).max())
+    over = np.abs(r["dp"] - r["dp_ref"]) > r["step_bound"]
+    print(f"drq adamw count {count}: mu' worst rel {rel(r['mu'], mu):.2e} ({int((np.abs(r['mu'] - mu) > 1e-6 * np.abs(mu)).sum())} "
+          f"of {p0.size} over 1e-6); "
+          f"nu' worst rel {rel(r['nu'], nu):.2e}; step worst err / bound "
+          f"{float((np.abs(r['dp'] - r['dp_ref']) / np.maximum(r['step_bound'], 1e-300)).max()):.3f} ({int(over.sum())} over)")
+    _adamw_runs[count] = r
+    return r
+
+
+def _adamw_common(r, count):
+    assert r["step"] == count + 1
+    np.testing.assert_allclose(r["nu"], r["nu_ref"], rtol=1e-6, atol=0)
+    np.testing.assert_allclose(r["tgt"], r["tgt_ref"], rtol=1e-6, atol=1e-6)
+    for key, want in (("metrics/critic_grad_magnitude", np.linalg.norm(r["g"])),
+                      ("metrics/critic_params_norm", np.linalg.norm(r["p0"]))):
+        assert abs(r["logs"][key] - want) <= 1e-5 * want, (key, r["logs"][key], want)
+
+
+@pytest.mark.parametrize("count", ADAM_COUNTS)
+def test_adamw_later_steps(count):
+    """AdamW with bias correction at count > 1 and non-zero moments (mu = 1e-3 N(0, 1), nu positive),
+    every element against float64 optax.adamw on the device's own gradient (held to the oracle in
+    test_update_matches_oracle): the step counter, the two logged norms, nu' to rtol 1e-6, the
+    Polyak target, mu' to rtol 1e-6 and the step to 2^-23 |p| (the rounding of the stored parameter)
+    plus 1e-5 |dp_ref| (a few ulp of the update).
+
+    Non-zero moments make (1 - b1) g and b1 mu nearly cancel on some elements (300 of 100305 here
+    past rtol 1e-6), where a float32 sum is off by up to 2^-23 of the |terms| -- 5.84e-4 of the
+    result on the worst element, and 2.05x the step's bar on a few parameters at zero (measured with
+    the kernel's earlier float32 arithmetic).  adamw_kernel therefore forms the element update in
+    double from the float32 operands and rounds each stored value once."""
+    r = _adamw_step(count)
+    _adamw_common(r, count)
+    np.testing.assert_allclose(r["mu"], r["mu_ref"], rtol=1e-6, atol=0)
+    assert (np.abs(r["dp"] - r["dp_ref"]) <= r["step_bound"]).all()
 
 
 @pytest.mark.parametrize("hw,B", [(20, 8), (84, 16), (84, 256)], ids=["small", "reference_geometry", "b256"])
