@@ -55,6 +55,15 @@ int mtsac_debug_x3p_geo(int geo);
  * Csum (nullable): sum of the written output planes.  -95 when the kernel does not take the shape. */
 int mtsac_debug_gemm_x3f(int epi, int batch, int M, int N, int K, const float* A, const float* B, float* C,
                          const float* bias, const float* mask, float* Csum);
+/* The ragged split2h data grad of the actor step (gemm_x3f_ragged, E = 2) beside the dense launch it
+ * replaces, on host arrays at any tile count: A [2][B][K], W [2][N][K], mask [2][B][N], active [2][B]
+ * bytes.  Dense: A with the inactive rows zeroed; ragged: the active rows compacted in ascending order.
+ * flags bit 0: planes out (else fp32), bit 1: W in the fragment layout.  dense_out / rag_out: fp32
+ * [2][B][N] or the two fp16 planes as 16-bit words [2][2][B][N] (ragged: rows at their slots, the rest
+ * left at 0xFF bytes); rows_out [2][B]: the lists; info [6]: dense / ragged output exponent, dense /
+ * ragged max over the record's partial maxima (float bits; the ragged record starts at 1e30), n_0, n_1. */
+int mtsac_debug_gemm_x3f_ragged(int flags, int B, int N, int K, const float* A, const float* W, const float* mask,
+                                const unsigned char* active, void* dense_out, void* rag_out, int* rows_out, int* info);
 /* Time iters launches of the forward-shaped plane GEMM: which 0 = gemm_x3p (B k-major), 1 = gemm_x3f,
  * -1 = gemm_x3s (-2 / -3: its TI = 7 instance without operand loads / without MFMAs, experiments);
  * epi bits 8-9: outputs 0 = fp32 + planes, 1 = planes only, 2 = fp32 only; bit 10: precision bf16;
@@ -143,6 +152,12 @@ int mtsac_debug_head_selfcheck(struct mtsac_engine* engine);
  * default) decides by shape (MTSAC_BFRAG=0 turns it off), 0 / 1 forces it off / allows it, for
  * engines created afterwards.  mtsac_debug_bfrag: bit i actor layer i, bit 8 + i critic layer i. */
 int mtsac_debug_set_bfrag(int32_t mode);
+/* The actor step's pass through the critic over each member's active rows only (rows whose dq is not
+ * zero; engine.cpp actor_compact): mode -1 (the default) follows MTSAC_ACTOR_DENSE (1: the dense pass),
+ * 0 / 1 forces compacted-where-it-applies / dense, for engines created afterwards. */
+int mtsac_debug_set_actor_dense(int32_t mode);
+/* 1 when the last step this engine issued (or captured) ran that pass compacted, else 0. */
+int mtsac_debug_actor_compact(struct mtsac_engine* engine);
 int mtsac_debug_bfrag(struct mtsac_engine* engine);
 /* on != 0: this engine issues on one stream whatever MTSAC_LANES asks, and is not counted by the
  * lane grant of the other live engines (experiments comparing the two issue forms in one process). */

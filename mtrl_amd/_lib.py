@@ -159,6 +159,7 @@ SIGNATURES = {
     "mtsac_debug_gemm_x3p_bench": (ctypes.c_int, [ctypes.c_int] * 6 + [PD]),
     "mtsac_debug_x3p_geo": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_gemm_x3f": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 6),
+    "mtsac_debug_gemm_x3f_ragged": (ctypes.c_int, [ctypes.c_int] * 4 + [P] * 8),
     "mtsac_debug_gemm_fwd_bench": (ctypes.c_int, [ctypes.c_int] * 7 + [PD]),
     "mtsac_debug_x3s_ti": (ctypes.c_int, [ctypes.c_int] * 3),
     "mtsac_debug_drq_groups": (ctypes.c_int, [ctypes.c_int] * 2),
@@ -177,6 +178,8 @@ SIGNATURES = {
     "mtsac_debug_read": (ctypes.c_int, [P, ctypes.c_int32, P, ctypes.c_int64]),
     "mtsac_debug_head_selfcheck": (ctypes.c_int, [P]),
     "mtsac_debug_set_bfrag": (ctypes.c_int, [ctypes.c_int32]),
+    "mtsac_debug_set_actor_dense": (ctypes.c_int, [ctypes.c_int32]),
+    "mtsac_debug_actor_compact": (ctypes.c_int, [P]),
     "mtsac_debug_bfrag": (ctypes.c_int, [P]),
     "mtsac_debug_force_one_stream": (ctypes.c_int, [P, ctypes.c_int32]),
     "mtsac_debug_set_collective_model": (ctypes.c_int, [P, ctypes.c_int32, ctypes.c_double, ctypes.c_int32]),

@@ -420,6 +420,151 @@ int mtsac_debug_gemm_x3f(int epi, int batch, int M, int N, int K, const float* A
   return 0;
 }
 
+// The ragged split2h data grad (gemm_x3f_ragged) beside the dense launch it replaces, on host arrays, E = 2:
+// A [2][B][K] (dz), W [2][N][K], mask [2][B][N] (the activation), active [2][B] bytes.  The dense launch runs
+// on A with the inactive rows zeroed; the ragged one on A's active rows compacted in ascending row order
+// (lists from active_rows on dq = active ? -1 : 0), both at the same plane exponents, whatever the tile
+// count (the engine's >= 192-workgroup policy is not asked).  flags bit 0: planes out (else fp32), bit 1:
+// W planes in the fragment layout (N % 16 == 0).  dense_out / rag_out: fp32 [2][B][N], or the two fp16
+// planes as 16-bit words [2][2][B][N]; the ragged buffer and its record's partial maxima start as 0xFF
+// bytes / 1e30.  rows_out [2][B]: the lists (0xFF words past n_e).  info [6]: the dense and ragged output
+// exponents, the max over the partial maxima of each (float bits), n_0, n_1.
+int mtsac_debug_gemm_x3f_ragged(int flags, int B, int N, int K, const float* A, const float* W, const float* mask,
+                                const unsigned char* active, void* dense_out, void* rag_out, int* rows_out,
+                                int* info) {
+  const bool pout = flags & 1, bfrag = (flags >> 1) & 1;
+  if (B < 1 || N < 8 || N % 8 != 0 || K < 1 || !A || !W || !mask || !active || !dense_out || !rag_out || !rows_out ||
+      !info || (bfrag && N % 16 != 0))
+    return -22;
+  const int E = 2;
+  const size_t nA = (size_t)E * B * K, nW = (size_t)E * N * K, nC = (size_t)E * B * N;
+  // host: dq, A with the inactive rows zeroed
+  std::vector<float> dq((size_t)E * B), Az(A, A + nA);
+  for (int e = 0; e < E; ++e)
+    for (int b = 0; b < B; ++b) {
+      const bool on = active[(size_t)e * B + b] != 0;
+      dq[(size_t)e * B + b] = on ? -1.f : 0.f;
+      if (!on) std::fill(Az.begin() + ((size_t)e * B + b) * K, Az.begin() + ((size_t)e * B + b + 1) * K, 0.f);
+    }
+  Guarded gd;
+  float* d_dq = gd.in(dq.data(), dq.size());
+  float* dAz = gd.in(Az.data(), nA);
+  float* dW = gd.in(W, nW);
+  float* dmask = gd.in(mask, nC);
+  int* d_n = gd.out<int>(E, "n");
+  int* d_rows = gd.out<int>((size_t)E * B, "rows");
+  int* d_slot = gd.out<int>((size_t)E * B, "slot");
+  if (!gd.ok) return -12;
+  active_rows(d_dq, E, B, d_n, d_rows, d_slot, nullptr);
+  if (int rc = sync_rc("active_rows")) return rc;
+  std::vector<int> hn(E), hrows((size_t)E * B);
+  if (!gd.back(hn.data(), d_n, E) || !gd.back(hrows.data(), d_rows, hrows.size())) return -5;
+  for (int e = 0; e < E; ++e)
+    if (hn[e] < 0 || hn[e] > B) return -5;
+  std::vector<float> Ac(nA, 0.f);  // compacted (rows past n_e: zeros, never read)
+  for (int e = 0; e < E; ++e)
+    for (int s2 = 0; s2 < hn[e]; ++s2) {
+      const int b = hrows[(size_t)e * B + s2];
+      if (b < 0 || b >= B) return -5;
+      std::copy(Az.begin() + ((size_t)e * B + b) * K, Az.begin() + ((size_t)e * B + b + 1) * K,
+                Ac.begin() + ((size_t)e * B + s2) * K);
+    }
+  float* dAc = gd.in(Ac.data(), nA);
+  // records: A, W, mask, dense out, ragged out
+  auto amax = [](const float* x, size_t n) {
+    float m = 0.f;
+    for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(x[i]));
+    return m;
+  };
+  auto pexp = [](float b) {
+    b *= 1.00390625f;
+    if (!(b > 0.f)) return 0;
+    int ex;
+    (void)std::frexp(b, &ex);
+    return 15 - ex;
+  };
+  std::vector<PlaneRec> hrec(5);
+  std::memset(hrec.data(), 0, sizeof(PlaneRec) * hrec.size());
+  const float ma = amax(Az.data(), nA), mw = amax(W, nW), mm = amax(mask, nC);
+  hrec[0].e = pexp(ma); hrec[0].amax[0] = ma;
+  hrec[1].e = pexp(mw); hrec[1].amax[0] = mw;
+  hrec[2].e = pexp(mm); hrec[2].amax[0] = mm;
+  hrec[3].e = hrec[4].e = 0x7fffffff;
+  for (int i = 0; i < PLANE_REC_PARTS; ++i) hrec[3].amax[i] = hrec[4].amax[i] = 1e30f;  // poison: a stale slot shows
+  PlaneRec* rec = gd.in(hrec.data(), hrec.size());
+  const long long Kp = (K + 63) / 64 * 64;
+  __bf16* Azp = gd.mem.get<__bf16>((size_t)3 * B * Kp * E);
+  __bf16* Acp = gd.mem.get<__bf16>((size_t)3 * B * Kp * E);
+  __bf16* Wp = gd.mem.get<__bf16>((size_t)3 * N * Kp * E);
+  __bf16* Mp = gd.mem.get<__bf16>(3 * nC);
+  const size_t out_bytes = pout ? nC * 2 * sizeof(__bf16) : nC * sizeof(float);
+  unsigned char* dden = gd.out<unsigned char>(out_bytes, "dense out");
+  unsigned char* drag = gd.out<unsigned char>(out_bytes, "ragged out");
+  if (!gd.ok || !dAc || !rec || !Azp || !Acp || !Wp || !Mp) return -12;
+  for (int z = 0; z < E; ++z) {
+    SplitParams sp{};
+    sp.ldx = K; sp.rows = B; sp.cols = K; sp.ldo = Kp; sp.po = (long long)B * Kp; sp.out_rows = B; sp.out_cols = (int)Kp;
+    sp.e2h = &rec[0].e;
+    sp.x = dAz + (size_t)z * B * K; sp.out = Azp + (size_t)z * 3 * B * Kp;
+    split_planes(sp, false, 1, nullptr);
+    sp.x = dAc + (size_t)z * B * K; sp.out = Acp + (size_t)z * 3 * B * Kp;
+    split_planes(sp, false, 1, nullptr);
+    sp.x = dW + (size_t)z * N * K; sp.rows = N; sp.out = Wp + (size_t)z * 3 * N * Kp; sp.po = (long long)N * Kp;
+    sp.out_rows = N; sp.e2h = &rec[1].e; sp.frag = bfrag ? 1 : 0;
+    split_planes(sp, false, 1, nullptr);
+    sp.frag = 0;
+    sp.x = dmask + (size_t)z * B * N; sp.ldx = N; sp.rows = B; sp.cols = N;
+    sp.out = Mp + (size_t)z * 3 * B * N; sp.ldo = N; sp.po = (long long)B * N; sp.out_rows = B; sp.out_cols = N;
+    sp.e2h = &rec[2].e;
+    split_planes(sp, false, 1, nullptr);
+  }
+  SplitGemmParams g{};
+  g.np = 2;
+  g.lda = Kp; g.pA = (long long)B * Kp; g.sA = 3 * g.pA;
+  g.B = Wp; g.ldb = Kp; g.pB = (long long)N * Kp; g.sB = 3 * g.pB;
+  g.b_frag = bfrag ? 1 : 0;
+  g.mask16 = Mp; g.ldm = N; g.sMask = 3ll * B * N; g.pMask = (long long)B * N;
+  g.M = B; g.N = N; g.K = (int)Kp;
+  g.ra = rec + 0; g.na = 1;
+  g.rb = rec + 1; g.nb = 1;
+  g.kmul = (float)K;
+  int nparts[2] = {0, 0};
+  auto outs = [&](unsigned char* o, PlaneRec* rc, int* np_) {
+    g.C = nullptr; g.Cp = nullptr; g.rc = nullptr;
+    if (pout) {
+      g.Cp = reinterpret_cast<__bf16*>(o); g.ldcp = N; g.pC = (long long)B * N; g.sCp = 2 * g.pC;
+      g.rc = rc;
+    } else {
+      g.C = reinterpret_cast<float*>(o); g.ldc = N; g.sC = (long long)B * N;
+    }
+    g.nparts = np_;
+  };
+  g.A = Azp;
+  outs(dden, rec + 3, &nparts[0]);
+  gemm_x3f(g, EPI_RELU_MASK, E, nullptr);  // no workspace: the plain unsplit launch
+  if (int rc = sync_rc("dense gemm_x3f")) return rc;
+  g.A = Acp;
+  outs(drag, rec + 4, &nparts[1]);
+  g.rag_n = d_n; g.rag_rows = d_rows; g.rag_ld = B;
+  gemm_x3f_ragged(g, nullptr);
+  if (int rc = sync_rc("gemm_x3f_ragged")) return rc;
+  if (int rc = gd.check()) return rc;
+  if (!gd.back(reinterpret_cast<unsigned char*>(dense_out), dden, out_bytes) ||
+      !gd.back(reinterpret_cast<unsigned char*>(rag_out), drag, out_bytes) ||
+      !gd.back(hrec.data(), rec, hrec.size()))
+    return -5;
+  std::copy(hrows.begin(), hrows.end(), rows_out);
+  for (int k = 0; k < 2; ++k) {
+    float m = 0.f;
+    for (int i = 0; i < nparts[k] && i < PLANE_REC_PARTS; ++i) m = std::max(m, hrec[3 + k].amax[i]);
+    info[k] = hrec[3 + k].e;
+    std::memcpy(&info[2 + k], &m, sizeof(float));
+  }
+  info[4] = hn[0];
+  info[5] = hn[1];
+  return 0;
+}
+
 // time iters launches of the forward-shaped plane GEMM (C = relu(A . B^T + bias) with planes out)
 // on device-resident random planes; which: 0 = gemm_x3p (row-major A, k-major B: the engine's
 // current forward), 1 = gemm_x3f (row-major both)

@@ -36,6 +36,7 @@ namespace {
 
 thread_local std::string g_last_error;
 int g_bfrag_mode = -1;  // mtsac_debug_set_bfrag: -1 by shape (and MTSAC_BFRAG), 0 off, 1 allowed
+int g_actor_dense_mode = -1;  // mtsac_debug_set_actor_dense: -1 by MTSAC_ACTOR_DENSE, 0 compacted, 1 dense
 
 int fail(int code, const std::string& msg) {
   g_last_error = msg;
@@ -322,6 +323,14 @@ struct mtsac_engine {
   float *logpi_n = nullptr, *logpi = nullptr, *y = nullptr, *dq = nullptr, *row_a = nullptr, *row_b = nullptr,
         *row_c = nullptr, *alpha_w = nullptr, *cache = nullptr, *dout_a = nullptr;
   float* partials = nullptr;
+  // The actor step's pass through the critic (s_ap) over each member's active rows only: the loss takes
+  // the min over the two members, so dq of the other member is exactly 0 and that member's row of every
+  // data grad is 0 from end to end.  act_n [E], act_rows / act_slot [E][B] from
+  // active_rows; actor_dense (MTSAC_ACTOR_DENSE=1 or mtsac_debug_set_actor_dense, read at create) keeps
+  // the dense pass.
+  int *act_n = nullptr, *act_rows = nullptr, *act_slot = nullptr;
+  bool actor_dense = false;
+  int actor_compact_last = 0;  // the last issued (or captured) step's pass ran compacted (mtsac_debug_actor_compact)
   // split-K workspaces, one per lane: segments on different lanes may run concurrently, the
   // segments of one lane are ordered by the step DAG (see seg())
   float* ws_lane[5] = {};
@@ -730,9 +739,13 @@ struct mtsac_engine {
   // head backward into the top layer's data grad.  With planes the GEMMs read only the planes: the
   // fp32 dz is skipped and (want_db) the bias grad's column sums come out of the same pass.
   void head_bwd(Net& net, const HeadParams& hp, const float* dout, long long s_dout, float** dz, __bf16** dzp,
-                bool want_db) {
+                bool want_db, const int* slot = nullptr) {
     const int top = net.depth - 1;
     const PlaneOut po = top_planes(net, dzp);
+    if (slot != nullptr) {  // compacted (actor_compact's conditions: planes, no bias grad)
+      head_backward_data(hp, dout, s_dout, nullptr, counts, rows, B, T_l, cur, po, nullptr, slot);
+      return;
+    }
     if (po.p == nullptr) {
       head_backward_data(hp, dout, s_dout, dz[top], counts, rows, B, T_l, cur, po);
       net.dbp_chunks[top] = 0;
@@ -997,8 +1010,11 @@ struct mtsac_engine {
   // column sums are wanted; without it (the actor step's pass through the critic) only the data
   // flows on.  Hidden layers on gemm_x3f keep planes only: their bias grad comes from the
   // epilogue's column sums.
-  void dgrad_layer(Net& net, const float* params, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
-                   int M, bool want_db = true) {
+  // rag: 0 the dense launch; 1 the launch over the members' active rows (gemm_x3f_ragged: dz[i]'s planes
+  // are compacted, so are the outputs); 2 launches nothing and returns whether 1 may be used here
+  bool dgrad_layer(Net& net, const float* params, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
+                   int M, bool want_db = true, int rag = 0) {
+    if (rag != 0 && !(planes && dzp && h2 && net.x3f && !want_db)) return false;
     if (planes && dzp) {  // NT on planes: dz[i] . W_i^T, W_i planes read as [N = in][K = out]
       SplitGemmParams g{};
       g.np = np;
@@ -1036,7 +1052,30 @@ struct mtsac_engine {
       g.ws = ws_lane[cur_lane];
       g.cnt = fin_cnt();
       g.pMask = net.aps();
+      if (rag == 2) {  // the probe leaves the records alone
+        if (g.Cp) g.C = nullptr;
+        return gemm_x3f_ragged_ok(g, EPI_RELU_MASK, net.E);
+      }
       if (h2) h2_gemm(g, &dz_rec(dzp)[i], &w_rec(net, 0), g.Cp ? &dz_rec(dzp)[i - 1] : nullptr, (float)net.width, false);
+      if (rag == 1) {
+        if (g.Cp) g.C = nullptr;
+        g.rag_n = act_n;
+        g.rag_rows = act_rows;
+        g.rag_ld = M;
+        // the members' active rows add up to M (more only on exact ties): M rows of products, not E M
+        t_begin(MTSAC_FAM_DATA_GRAD, 2.0 * (double)g.M * g.N * g.K);
+        if (timing) {
+          tl[tl_next].M = g.M;
+          tl[tl_next].N = g.N;
+          tl[tl_next].K = g.K;
+          tl[tl_next].batch = 1;
+        }
+        gemm_x3f_ragged(g, cur);
+        fam_kernel[MTSAC_FAM_DATA_GRAD] = std::string("gemm_x3f_kernel<208, 2, ") + (g.C ? "true" : "false") + ", " +
+                                          (g.Cp ? "true" : "false") + ", true, 16, 2>";
+        t_end();
+        return true;
+      }
       if (g.Cp) {  // dz[i-1]'s fp32 copy only feeds the bias grad's column sums
         if (!want_db) {
           g.C = nullptr;
@@ -1053,7 +1092,7 @@ struct mtsac_engine {
         }
       }
       gemmp(g, EPI_RELU_MASK, net.E, MTSAC_FAM_DATA_GRAD);
-      return;
+      return true;
     }
     GemmParams g{};
     g.A = dz[i];
@@ -1072,7 +1111,21 @@ struct mtsac_engine {
     g.N = net.width;
     g.K = net.width;
     gemm(g, GEMM_NT, EPI_RELU_MASK, net.E, MTSAC_FAM_DATA_GRAD);
+    return true;
   }
+
+  // the actor step's pass through the critic runs compacted: split2h planes, two members, hidden layers,
+  // and every data grad of the pass would be the plain unsplit gemm_x3f launch (task shards on split-K,
+  // gemm_x3s / gemm_x3p shapes and the other precisions keep the dense pass)
+  bool actor_compact(int M) {
+    if (actor_dense || !h2 || !planes || critic.E != 2 || critic.hd != 1 || critic.depth < 2 || critic.width % 4 != 0 ||
+        top_planes_ptr(critic, dzcp) == nullptr)
+      return false;
+    for (int i = critic.depth - 1; i > 0; --i)
+      if (!dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, M, false, 2)) return false;
+    return true;
+  }
+  __bf16* top_planes_ptr(Net& net, __bf16** dzp) const { return planes && net.depth > 1 ? dzp[net.depth - 1] : nullptr; }
 
   HeadParams head(Net& net, const float* params, const float* h, int M, const int* tsk) {
     HeadParams hp{};
@@ -1728,10 +1781,15 @@ struct mtsac_engine {
         c.dq_parts = &r_dq.n;
       }
       critic_head(c, cur);
-      head_bwd(critic, c.head, dq, Bl, dzc, dzcp, false);
-      for (int i = critic.depth - 1; i > 0; --i) dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, Bl, false);
+      const bool rag = actor_compact(Bl);  // each member's rows with dq != 0 only
+      actor_compact_last = rag ? 1 : 0;
+      if (rag) active_rows(dq, critic.E, Bl, act_n, act_rows, act_slot, cur);
+      head_bwd(critic, c.head, dq, Bl, dzc, dzcp, false, rag ? act_slot : nullptr);
+      for (int i = critic.depth - 1; i > 0; --i)
+        dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, Bl, false, rag ? 1 : 0);
       ActionGradParams ag{};
       ag.dz1 = dzc[0];
+      ag.slot = rag ? act_slot : nullptr;
       ag.W0 = critic.p + critic.off_W[0];
       ag.s_dz = (long long)Bl * critic.width;
       ag.s_W0 = critic.ms_W[0];
@@ -2630,6 +2688,14 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
     if ((rc = e->alloc(&e->cs_part, (size_t)std::max(1, c.num_critics) * COLSUM_CHUNKS * wmax))) return bad(rc);
   }
   if ((rc = e->alloc(&e->dq, (size_t)c.num_critics * B))) return bad(rc);
+  // the active-row lists at their worst case: every row of every member (all ties)
+  if ((rc = e->alloc(&e->act_n, (size_t)std::max(2, c.num_critics)))) return bad(rc);
+  if ((rc = e->alloc(&e->act_rows, (size_t)c.num_critics * B))) return bad(rc);
+  if ((rc = e->alloc(&e->act_slot, (size_t)c.num_critics * B))) return bad(rc);
+  {
+    const char* v = getenv("MTSAC_ACTOR_DENSE");
+    e->actor_dense = g_actor_dense_mode >= 0 ? g_actor_dense_mode != 0 : (v && atoi(v) != 0);
+  }
   if ((rc = e->alloc(&e->cache, (size_t)B * 5 * e->A))) return bad(rc);
   if ((rc = e->alloc(&e->dout_a, (size_t)B * 2 * e->A))) return bad(rc);
   if ((rc = e->alloc(&e->partials, 2 * PART))) return bad(rc);  // elementwise + tiled update
@@ -3659,6 +3725,17 @@ int mtsac_debug_set_bfrag(int32_t mode) {
   if (mode < -1 || mode > 1) return fail(-22, "bfrag mode is -1, 0 or 1");
   g_bfrag_mode = mode;
   return 0;
+}
+
+int mtsac_debug_set_actor_dense(int32_t mode) {
+  if (mode < -1 || mode > 1) return fail(-22, "actor dense mode is -1, 0 or 1");
+  g_actor_dense_mode = mode;
+  return 0;
+}
+
+int mtsac_debug_actor_compact(mtsac_engine* h) {
+  if (!h) return fail(-22, "null engine");
+  return h->actor_compact_last;
 }
 
 int mtsac_debug_bfrag(mtsac_engine* h) {

@@ -259,6 +259,23 @@ bool gemm_x3f_ok(const SplitGemmParams& p, int epi, int batch) {
          (!p.b_frag || (p.N % 16 == 0 && p.ldb % 32 == 0));
 }
 
+bool gemm_x3f_ragged_ok(const SplitGemmParams& p, int epi, int batch) {
+  return p.np == 2 && batch == 2 && epi == EPI_RELU_MASK && p.mask16 != nullptr && p.dbp == nullptr &&
+         (p.C != nullptr) != (p.Cp != nullptr) && x3fk::g_x3f_order == 0 && gemm_x3f_ok(p, epi, batch) &&
+         x3f_slices(p, epi, batch) == 1;
+}
+
+void gemm_x3f_ragged(const SplitGemmParams& p, hipStream_t st) {
+  using namespace x3fk;
+  // the dense grid: every row of both members active (all ties) is the worst case
+  const dim3 grid((unsigned)(((p.M + BM0 - 1) / BM0) * ((p.N + BN - 1) / BN) * 2));
+  if (p.nparts) *p.nparts = (int)grid.x;  // the workgroups past the live tiles write a zero maximum
+  if (p.Cp != nullptr)
+    hipLaunchKernelGGL((gemm_x3f_kernel<BM0, EPI_RELU_MASK, false, true, true, TAG_RAGGED, 2>), grid, dim3(512), 0, st, p);
+  else
+    hipLaunchKernelGGL((gemm_x3f_kernel<BM0, EPI_RELU_MASK, true, false, true, TAG_RAGGED, 2>), grid, dim3(512), 0, st, p);
+}
+
 int gemm_x3f(const SplitGemmParams& p0, int epi, int batch, hipStream_t st) {
   using namespace x3fk;
   const int S = x3f_slices(p0, epi, batch);

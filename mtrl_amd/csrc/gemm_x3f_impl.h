@@ -22,6 +22,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BN = 256;  // 8 waves x 32 columns
 constexpr int TAG_INPUT = 8;
+constexpr int TAG_RAGGED = 16;  // ABL tag of the ragged data grad (RAG below)
 constexpr int KS = 64;   // k per stage / main-loop step
 
 // One B fragment: 16 B of row n at byte offset voff from the wave-uniform base (no compiler wait)
@@ -69,6 +70,11 @@ __device__ inline void wait_vm(bf16x8 (&b)[JB][NP]) {
 // two row tiles' MFMA chains changed nothing there).
 // ABL == TAG_INPUT changes nothing: it only gives input-layer launches their own kernel symbol, so
 // rocprof stats and PMC passes separate them from the hidden layers.
+// ABL == TAG_RAGGED (RAG; split2h data grad of a two-member ensemble, E = 2): member z holds only
+// p.rag_n[z] rows, compacted (A and the outputs at slot s; the ReLU mask at the original batch row
+// p.rag_rows[z * p.rag_ld + s]).  The launch has the dense worst-case grid; every workgroup derives
+// the live tile count L from rag_n, the XCD remap runs over L (so the live tiles use all eight XCDs),
+// and a workgroup past L zeroes its partial-max slot and leaves.
 // NP: operand planes read (3: 6 products, fp32-accurate; 1: the high plane only, precision bf16;
 // 2: precision split2h -- two fp16 planes of x 2^e per operand, 3 products h*l, l*h, h*h, the
 // accumulator unscaled by 2^-(eA + eB) in the epilogue, output planes at the exponent of the bound)
@@ -124,9 +130,23 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_x3f_kernel(SplitGemmParams p)
   const int mine = (wave < NJ % WV || NJ % WV == 0) ? PMAX : PMAX - 1;  // DMA pieces of this wave
 
   // XCD-contiguous tile order (as gemm_x3p): N tile fastest inside an XCD's run
+  constexpr bool RAG = ABL == TAG_RAGGED;
+  static_assert(!RAG || (NP == 2 && !FIN && EPI == EPI_RELU_MASK && MASK16), "ragged: the split2h data grad only");
   const int ny = (p.N + BN - 1) / BN, nx = (p.M + BM - 1) / BM;
   int lin = blockIdx.x;
-  {
+  int rag_t0 = 0, rag_n0 = 0, rag_n1 = 0;  // RAG: member 0's row tiles, the members' rows
+  if constexpr (RAG) {
+    rag_n0 = min(max(p.rag_n[0], 0), p.M);
+    rag_n1 = min(max(p.rag_n[1], 0), p.M);
+    rag_t0 = (rag_n0 + BM - 1) / BM;
+    const int n = min((rag_t0 + (rag_n1 + BM - 1) / BM) * ny, (int)gridDim.x);  // live tiles
+    if (lin >= n) {  // (block-uniform) no stale maximum in this workgroup's slot
+      if (P_OUT && t == 0 && lin < PLANE_REC_PARTS) p.rc->amax[lin] = 0.f;
+      return;
+    }
+    const int q8 = n / 8, r8 = n % 8, x = lin % 8;
+    lin = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + lin / 8;
+  } else {
     const int n = gridDim.x, q8 = n / 8, r8 = n % 8, x = lin % 8;
     lin = (x < r8 ? x * (q8 + 1) : r8 * (q8 + 1) + (x - r8) * q8) + lin / 8;
   }
@@ -134,11 +154,14 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_x3f_kernel(SplitGemmParams p)
   const int nsplit = p.splits > 1 ? p.splits : 1;
   const int tiles = ny * nx * (int)(gridDim.x / nsplit / (ny * nx));
   // FIN: a tile's slices adjacent (one XCD: the last arriver reads same-XCD slabs); else slice-major
-  const int sl = FIN ? lin % nsplit : lin / tiles;
-  lin = FIN ? lin / nsplit : lin - sl * tiles;
+  const int sl = RAG ? 0 : FIN ? lin % nsplit : lin / tiles;
+  lin = RAG ? lin : FIN ? lin / nsplit : lin - sl * tiles;
   const int tile_id = lin;
-  const int by = p.order ? (lin / nx) % ny : lin % ny, bx = p.order ? lin % nx : (lin / ny) % nx;
-  const int z = lin / (ny * nx);
+  // RAG: column tiles fastest; row tile lin / ny of member 0's rag_t0 tiles followed by member 1's
+  const int by = RAG ? lin % ny : p.order ? (lin / nx) % ny : lin % ny;
+  const int bx = RAG ? lin / ny - (lin / ny >= rag_t0 ? rag_t0 : 0) : p.order ? lin % nx : (lin / ny) % nx;
+  const int z = RAG ? (lin / ny >= rag_t0 ? 1 : 0) : lin / (ny * nx);
+  const int Mz = RAG ? (z ? rag_n1 : rag_n0) : p.M;  // rows of this member (>= 1 in a live tile)
   const int m0 = bx * BM, n0 = by * BN;
   const int k0 = nsplit > 1 ? sl * p.kchunk : 0;
   const __bf16* __restrict__ A = p.A + z * p.sA + k0;
@@ -153,7 +176,7 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_x3f_kernel(SplitGemmParams p)
     int row = m0 + 8 * rg + (lane >> 3);
     const int pc = lane & 7;                       // physical 16-B chunk
     const int c = pc ^ (row & 7);                  // logical chunk it holds (8 k each)
-    row = row < p.M ? row : p.M - 1;               // rows past M feed discarded outputs
+    row = row < Mz ? row : Mz - 1;                 // rows past M feed discarded outputs
     glds16(A + q * p.pA + (long long)row * p.lda + k0 + 8 * c, st + q * PLANE + rg * 1024);
   };
   auto wave_piece = [&](int qi, int k0, unsigned st) {  // this wave's qi-th piece of a stage
@@ -499,7 +522,8 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_x3f_kernel(SplitGemmParams p)
 #pragma unroll
       for (int rp = 0; rp < RP; ++rp) {
         int row = m0 + 16 * (i0 + g) + 2 * (wave + WV * rp) + (lane >> 5);
-        row = row < p.M ? row : p.M - 1;  // (rows past M are not stored)
+        row = row < Mz ? row : Mz - 1;  // (rows past M are not stored)
+        if constexpr (RAG) row = p.rag_rows[z * p.rag_ld + row];  // the mask lies at the batch row
         const __bf16* mp = p.mask16 + z * p.sMask + (long long)row * p.ldm + (colok ? col : 0);
         mbuf[b][g * RP + rp][0] = __builtin_bit_cast(i16x8, *reinterpret_cast<const bf16x8*>(mp));
         mbuf[b][g * RP + rp][1] = __builtin_bit_cast(i16x8, *reinterpret_cast<const bf16x8*>(mp + p.pMask));
@@ -534,7 +558,7 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_x3f_kernel(SplitGemmParams p)
     const float4 u = *reinterpret_cast<const float4*>(tb + orow * TS + oc);
     const float4 v = *reinterpret_cast<const float4*>(tb + orow * TS + oc + 4);
     const int row = m0 + 16 * i + orow;
-    if (row >= p.M || !colok) continue;
+    if (row >= Mz || !colok) continue;
     if ((ABL & 128) && p.M > 0) continue;  // ablation: no epilogue stores (p.M > 0 keeps the MFMAs live)
     float e[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
     if constexpr (NP == 2) {  // FIN: scale this slice's registers by unscale, as the slab's partial already is

@@ -449,11 +449,14 @@ __device__ inline void head_fault(unsigned* fault, unsigned bit) {
 }
 
 // (bx, by, bz) of a [W / 256][T_l HB_RS][E] grid; red: 4 x 64 float4 of LDS, chk: 4 x 64 digests
-template <int HD>
+// COMPACT (dz and dbp null): only the pairs (e, b) with slot[e * B + b] >= 0 are computed, into plane
+// row slot[e * B + b] (active_rows; the actor step's pass through the critic)
+template <int HD, bool COMPACT = false>
 __device__ inline void head_bwd_data_body(const HeadParams& hp, const float* __restrict__ dout, long long s_dout,
                                           float* __restrict__ dz, const PlaneOut& po_in, float* __restrict__ dbp,
                                           const int* __restrict__ counts, const int* __restrict__ rows, int max_rows,
-                                          int bx, int by, int bz, int gy, float4 (*red)[64], unsigned (*chk)[64]) {
+                                          int bx, int by, int bz, int gy, float4 (*red)[64], unsigned (*chk)[64],
+                                          const int* __restrict__ slot = nullptr) {
   // split2h: the planes' exponent from the bound kmul * max|dout| * (max|head weight| + w_add), every
   // workgroup alike (red is the scratch of the maxima); the scale rides in po.w_add from here on
   PlaneOut po = po_in;
@@ -488,6 +491,18 @@ __device__ inline void head_bwd_data_body(const HeadParams& hp, const float* __r
 #pragma unroll
       for (int u = 0; u < CH; ++u) bb[u] = rw[min(j0 + u * STRIDE, n - 1)];
       float4 o[CH];
+      if constexpr (COMPACT) {
+        int sl[CH];
+#pragma unroll
+        for (int u = 0; u < CH; ++u) sl[u] = j0 + u * STRIDE < n ? slot[(long long)e * hp.B + bb[u]] : -1;
+#pragma unroll
+        for (int u = 0; u < CH; ++u)
+          if (sl[u] >= 0) o[u] = head_bwd_val<HD>(hp, dout, s_dout, e, bb[u], w, wt);
+#pragma unroll
+        for (int u = 0; u < CH; ++u)
+          if (sl[u] >= 0) head_bwd_put<HD>(hp, e, sl[u], w, o[u], nullptr, po);
+        continue;
+      }
 #pragma unroll
       for (int u = 0; u < CH; ++u) o[u] = head_bwd_val<HD>(hp, dout, s_dout, e, bb[u], w, wt);
 #pragma unroll
@@ -525,6 +540,52 @@ __global__ __launch_bounds__(256) void head_bwd_data_kernel(HeadParams hp, const
   __shared__ unsigned chk[4][64];
   head_bwd_data_body<HD>(hp, dout, s_dout, dz, po, dbp, counts, rows, max_rows, blockIdx.x, blockIdx.y, blockIdx.z,
                          gridDim.y, red, chk);
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void head_bwd_data_compact_kernel(HeadParams hp, const float* __restrict__ dout,
+                                                                    long long s_dout, PlaneOut po,
+                                                                    const int* __restrict__ counts,
+                                                                    const int* __restrict__ rows, int max_rows,
+                                                                    const int* __restrict__ slot) {
+  __shared__ float4 red[4][64];
+  __shared__ unsigned chk[4][64];
+  head_bwd_data_body<HD, true>(hp, dout, s_dout, nullptr, po, nullptr, counts, rows, max_rows, blockIdx.x, blockIdx.y,
+                               blockIdx.z, gridDim.y, red, chk, slot);
+}
+
+// ------------------------------------------------------------------ active rows per ensemble member
+// block e: a scan over member e's dq in chunks of 1024 rows (ballot + popcount per wave, the waves'
+// totals through LDS), so rows[] is ascending and the same in every run
+__global__ __launch_bounds__(1024) void active_rows_kernel(const float* __restrict__ dq, int B, int* __restrict__ n_out,
+                                                           int* __restrict__ rows, int* __restrict__ slot) {
+  __shared__ int wtot[16];
+  const int e = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* d = dq + (long long)e * B;
+  int base = 0;
+  for (int b0 = 0; b0 < B; b0 += 1024) {
+    const int b = b0 + (int)threadIdx.x;
+    const bool on = b < B && d[b] != 0.f;
+    const unsigned long long m = __ballot(on);
+    const int pre = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wtot[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+      const int c = wtot[w];
+      off += w < wave ? c : 0;
+      tot += c;
+    }
+    if (b < B) {
+      const int s = base + off + pre;
+      slot[(long long)e * B + b] = on ? s : -1;
+      if (on) rows[(long long)e * B + s] = b;
+    }
+    base += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) n_out[e] = base;
 }
 
 // ------------------------------------------------------------------ head backward (weights)
@@ -908,6 +969,16 @@ __device__ inline float action_grad_rows(const ActionGradParams& p, int b0, int 
   for (int e = 0; e < p.E; ++e) {
     const float* dz = p.dz1 + e * p.s_dz;
     const float* W0 = p.W0 + e * p.s_W0;
+    // compacted dz1 (p.slot): a row whose member-e grad is zero is skipped -- the fmaf chain of a +0
+    // row returns its accumulator unchanged, so the sums are the dense ones, e = 0 then e = 1
+    int sl[AG_RW];
+    bool any = false;
+#pragma unroll
+    for (int r = 0; r < AG_RW; ++r) {
+      sl[r] = p.slot ? p.slot[(long long)e * p.B + rows[r]] : rows[r];
+      any = any || sl[r] >= 0;
+    }
+    if (!any) continue;  // (wave-uniform)
     if ((p.Wc & 3) == 0) {  // 16-B loads: lane l takes w = 4l + 256i .. +3
 #pragma unroll 2
       for (int w = 4 * lane; w < p.Wc; w += 256) {
@@ -918,7 +989,8 @@ __device__ inline float action_grad_rows(const ActionGradParams& p, int b0, int 
                                      : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int r = 0; r < AG_RW; ++r) {
-          const float4 g = *reinterpret_cast<const float4*>(dz + (long long)rows[r] * p.Wc + w);
+          if (sl[r] < 0) continue;
+          const float4 g = *reinterpret_cast<const float4*>(dz + (long long)sl[r] * p.Wc + w);
 #pragma unroll
           for (int j = 0; j < AM; ++j) {  // explicit fmas: the same roundings in every AG_RW instance
             float a = ga[r][j];
@@ -938,7 +1010,8 @@ __device__ inline float action_grad_rows(const ActionGradParams& p, int b0, int 
       for (int j = 0; j < AM; ++j) wv[j] = (AM == 4 || j < A) ? W0[(long long)j * p.Wc + w] : 0.f;
 #pragma unroll
       for (int r = 0; r < AG_RW; ++r) {
-        const float g = dz[(long long)rows[r] * p.Wc + w];
+        if (sl[r] < 0) continue;
+        const float g = dz[(long long)sl[r] * p.Wc + w];
 #pragma unroll
         for (int j = 0; j < AM; ++j) ga[r][j] = __builtin_fmaf(g, wv[j], ga[r][j]);
       }
@@ -1103,9 +1176,19 @@ void critic_head(const CriticHeadParams& p, hipStream_t st) {
   hipLaunchKernelGGL(critic_head_kernel, dim3(g), dim3(256), 0, st, p);
 }
 
+void active_rows(const float* dq, int E, int B, int* n, int* rows, int* slot, hipStream_t st) {
+  hipLaunchKernelGGL(active_rows_kernel, dim3((unsigned)E), dim3(1024), 0, st, dq, B, n, rows, slot);
+}
+
 void head_backward_data(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
-                        const int* rows, int max_rows, int T_l, hipStream_t st, PlaneOut po, float* dbp) {
+                        const int* rows, int max_rows, int T_l, hipStream_t st, PlaneOut po, float* dbp,
+                        const int* slot) {
   const dim3 grid((unsigned)((hp.W + 255) / 256), (unsigned)(T_l * HB_RS), (unsigned)hp.E);
+  if (slot != nullptr) {  // hd = 1 (the critic), planes only: the caller's conditions
+    hipLaunchKernelGGL(head_bwd_data_compact_kernel<1>, grid, dim3(256), 0, st, hp, dout, s_dout, po, counts, rows,
+                       max_rows, slot);
+    return;
+  }
 #define HBD_LAUNCH(HDV)                                                                                  \
   hipLaunchKernelGGL(head_bwd_data_kernel<HDV>, grid, dim3(256), 0, st, hp, dout, s_dout, dz, po, dbp, counts, \
                      rows, max_rows)

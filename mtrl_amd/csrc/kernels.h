@@ -153,6 +153,12 @@ struct SplitGemmParams {
   int* nparts;            // host: the launcher stores how many partial maxima it wrote to rc (or null)
   FinishSink* defer;      // host, gemm_x3p EPI_STORE: collect the finish (slab sums, bias grad) here
                           // instead of launching it (null: launch), when the sink has room
+  // ---- gemm_x3f_ragged only (the actor step's data grads through a two-member critic): member z holds
+  // rag_n[z] <= M compacted rows; row s of its A and outputs is batch row rag_rows[z * rag_ld + s],
+  // where the ReLU mask is read (active_rows)
+  const int* rag_n;
+  const int* rag_rows;
+  int rag_ld;
 };
 constexpr int GEMM_X3F_CNT = 4096;
 void gemm_x3p(const SplitGemmParams& p, int epi, int batch, hipStream_t st);
@@ -167,6 +173,11 @@ long long gemm_x3p_ws_floats(int M, int N, int K, int batch, bool kmajor);
 // (EPI_BIAS_RELU) and data grad (EPI_RELU_MASK) when gemm_x3f_ok
 bool gemm_x3f_ok(const SplitGemmParams& p, int epi, int batch);
 int gemm_x3f(const SplitGemmParams& p, int epi, int batch, hipStream_t st);  // returns the K slices used
+// The split2h ReLU-mask data grad of a two-member ensemble over the members' active rows only (p.rag_*;
+// one of C / Cp out, no column sums): the dense launch's worst-case grid, of which only the live tiles
+// run.  ok: the dense launch would be the plain unsplit gemm_x3f (gemm_x3f_ok, one K slice).
+bool gemm_x3f_ragged_ok(const SplitGemmParams& p, int epi, int batch);
+void gemm_x3f_ragged(const SplitGemmParams& p, hipStream_t st);
 int gemm_x3f_tiles(int M, int N, int batch);
 int gemm_x3f_row_tiles(int M);  // row tiles of M (the dbp partials' chunk count)
 int gemm_x3f_bm(const SplitGemmParams& p, int batch);  // row tile of an unsplit launch (208; bf16: 48..400)
@@ -371,9 +382,14 @@ struct PlaneOut {
 // walked per task (counts / rows of task_rows); dz may be null (planes only).  dbp (nullable):
 // column sums of dz per (task, row slice), [e][head_backward_chunks(T_l)][W], finished by
 // colsum_finish.  W % 4 == 0.
+// slot (nullable; hd = 1, planes only, no dz, no dbp): [E][B] from active_rows -- pairs (e, b) with
+// slot < 0 are skipped (their h is not read) and row b of member e is written at plane row slot[e][b].
 void head_backward_data(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
                         const int* rows, int max_rows, int T_l, hipStream_t st, PlaneOut po = PlaneOut{},
-                        float* dbp = nullptr);
+                        float* dbp = nullptr, const int* slot = nullptr);
+// Per member e of dq [E][B]: n[e] = the number of rows with dq[e][b] != 0, rows[e * B + s] = those rows in
+// ascending b, slot[e * B + b] = s or -1 (a block scan per member: the same lists in every run)
+void active_rows(const float* dq, int E, int B, int* n, int* rows, int* slot, hipStream_t st);
 int head_backward_chunks(int T_l);
 // head_backward_data + head_backward_weight of one head in one launch (false: W % 4 != 0, not launched)
 bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
@@ -390,6 +406,8 @@ void head_backward_weight(const HeadParams& hp, const float* dout, long long s_d
 // critic data grad into the action columns + tanh-normal backward -> actor head grad
 struct ActionGradParams {
   const float* dz1;     // [E][B][Wc]  grad at critic layer-0 pre-activation
+  const int* slot;      // nullable, [E][B] (active_rows): member e's dz1 row of batch row b lies at
+                        // slot[e][b]; < 0: the row is zero and the member is skipped for it
   const float* W0;      // [E][Ic][Wc] critic layer-0 kernel (rows 0..A-1 = action)
   long long s_dz, s_W0;
   int E, B, Wc, A;
