@@ -351,66 +351,19 @@ struct mtsac_engine {
   int cur_lane = 0;
 
   // Net::bfrag[li]: every GEMM that reads layer li's weight planes takes gemm_x3f (no other kernel
-  // reads the fragment layout).  The step's parameter sets (trunk_forward's x3f branch, dgrad_layer),
-  // probed with placeholder pointers after the workspaces exist; a mismatch with the step surfaces
-  // as gemmp's error, never as a silent fallback.
-  bool frag_probe(const Net& net, int li) {
-    static float f_;
-    static __bf16 h_;
-    float* F = &f_;
-    __bf16* H = &h_;
+  // reads the fragment layout).  Asked of the step's own builders (fwd_params, dgrad_params) on the
+  // step's buffers, at the row counts the step launches: B, the actor's merged forward over krows + B
+  // rows, the data grad with and without the bias grad's column sums.  Called at create once the
+  // workspaces and the activation / plane buffers exist.
+  bool frag_probe(Net& net, int li) {
     const bool is_actor = &net == &actor;
-    auto base = [&](int M, long long K, long long ldb) {
-      SplitGemmParams g{};
-      g.np = np;
-      g.lda = K;
-      g.ldb = ldb;
-      g.M = M;
-      g.N = net.width;
-      g.K = (int)K;
-      g.splits = -1;
-      g.ws = ws_lane[0];
-      g.cnt = fin_cnt();
-      g.b_frag = 1;
-      return g;
-    };
-    std::vector<int> fwd_rows = {B};
-    if (is_actor) fwd_rows.push_back((int)(net.krows + B));  // the merged [s | s'] forward
-    for (int M : fwd_rows)
-      for (int i = li; i == li; ++i) {
-        SplitGemmParams g = base(M, net.wtk(i), net.wtk(i));
-        g.bias = F;
-        if (i == net.depth - 1) {
-          g.C = F;
-          g.ldc = net.width;
-        } else {
-          g.Cp = H;
-          g.ldcp = net.ald;
-        }
-        if (!gemm_x3f_ok(g, EPI_BIAS_RELU, net.E)) return false;
-      }
-    for (int want_db = 0; want_db < 2; ++want_db)
-      for (int i = li; i == li && i > 0; ++i) {
-        SplitGemmParams g = base(B, net.ald, net.wld);
-        g.C = F;
-        g.ldc = net.width;
-        g.mask16 = H;
-        g.ldm = (int)net.ald;
-        if (i - 1 >= 1 || want_db) {
-          g.Cp = H;
-          g.ldcp = net.ald;
-        }
-        bool ok = false;
-        if (g.Cp && want_db) {
-          SplitGemmParams q = g;
-          q.C = nullptr;
-          q.dbp = F;
-          ok = gemm_x3f_ok(q, EPI_RELU_MASK, net.E);
-        } else if (g.Cp) {
-          g.C = nullptr;
-        }
-        if (!ok && !gemm_x3f_ok(g, EPI_RELU_MASK, net.E)) return false;
-      }
+    float **acts = is_actor ? ha : hc, **dz = is_actor ? dza : dzc;
+    __bf16 **actp = is_actor ? hap : hcp, **dzp = is_actor ? dzap : dzcp;
+    __bf16* xp = in_planes(is_actor ? xa : xc);
+    for (int M : {B, is_actor ? Ma : B})
+      if (!gemm_x3f_ok(fwd_params(net, net.p, 0, xp, acts, actp, li, M), EPI_BIAS_RELU, net.E)) return false;
+    for (int want_db = 0; want_db < 2 && li > 0; ++want_db)
+      if (!gemm_x3f_ok(dgrad_params(net, acts, actp, dz, dzp, li, B, want_db != 0), EPI_RELU_MASK, net.E)) return false;
     return true;
   }
   float* pn = nullptr;  // [critic trunk |p|^2, actor trunk, critic heads, actor heads]
@@ -632,7 +585,7 @@ struct mtsac_engine {
     if (r != hipSuccess) comm_error = std::string("stream fork/join: ") + hipGetErrorString(r);
   }
 
-  void t_begin(int family, double flops) {
+  void t_begin(int family, int M, int N, int K, int batch) {
     if (!timing) return;
     if (tl_next >= tl.size()) {
       TimedLaunch x{};
@@ -640,10 +593,14 @@ struct mtsac_engine {
       (void)hipEventCreate(&x.b);
       tl.push_back(x);
     }
-    tl[tl_next].family = family;
-    tl[tl_next].flops = flops;
-    tl[tl_next].M = tl[tl_next].N = tl[tl_next].K = tl[tl_next].batch = 0;
-    (void)hipEventRecord(tl[tl_next].a, cur);
+    TimedLaunch& t = tl[tl_next];
+    t.family = family;
+    t.flops = 2.0 * (double)M * N * K * batch;
+    t.M = M;
+    t.N = N;
+    t.K = K;
+    t.batch = batch;
+    (void)hipEventRecord(t.a, cur);
   }
   void t_end() {
     if (!timing) return;
@@ -653,13 +610,7 @@ struct mtsac_engine {
 
   // family: enum mtsac_gemm_family (timing only)
   void gemm(const GemmParams& p, GemmKind kind, int epi, int batch, int family) {
-    t_begin(family, 2.0 * (double)p.M * p.N * p.K * batch);
-    if (timing) {
-      tl[tl_next].M = p.M;
-      tl[tl_next].N = p.N;
-      tl[tl_next].K = p.K;
-      tl[tl_next].batch = batch;
-    }
+    t_begin(family, p.M, p.N, p.K, batch);
     if (planes)  // split3 / bf16: the plain fp32-operand GEMMs (input-layer weight grad) stay fp32-accurate
       gemm_x3(p, kind, epi, batch, cur);
     else
@@ -671,13 +622,7 @@ struct mtsac_engine {
   std::string fam_kernel[8];
 
   void gemmp(const SplitGemmParams& p, int epi, int batch, int family) {
-    t_begin(family, 2.0 * (double)p.M * p.N * p.K * batch);
-    if (timing) {
-      tl[tl_next].M = p.M;
-      tl[tl_next].N = p.N;
-      tl[tl_next].K = p.K;
-      tl[tl_next].batch = batch;
-    }
+    t_begin(family, p.M, p.N, p.K, batch);
     if (gemm_x3f_ok(p, epi, batch)) {
       const bool split = gemm_x3f(p, epi, batch, cur) > 1;
       // the rocprof symbol: gemm_x3f_kernel<BM, EPI, C_OUT, P_OUT, MASK16, TAG, NP> (split-K launches
@@ -769,6 +714,170 @@ struct mtsac_engine {
     return true;
   }
 
+  // ------------------------------------------------------------ the trunk's plane GEMMs: launch parameters
+  // One author per kind.  The step (trunk_forward, dgrad_layer, wgrad_layer), the layout probes
+  // (frag_probe, actor_compact) and the split-K workspace sizing in mtsac_create all take a launch's
+  // operands, shape and outputs from these three; the step adds only the split2h records (h2_gemm).
+  // The sizing runs before the buffers exist: it reads the shape fields, the pointers are null then.
+
+  // Forward of layer i over M rows (EPI_BIAS_RELU): in_i . W_i + b_i, in_i = xp (the input's planes) or
+  // actp[i - 1]; which 0 / 1: params is Net::p / Net::tgt.  net.x3f: both operands row-major, against the
+  // W_i^T planes (gemm_x3f / gemm_x3s), and hidden activations keep planes only; else against W_i's
+  // k-major planes (gemm_x3p), fp32 output at every layer.
+  SplitGemmParams fwd_params(Net& net, const float* params, int which, const __bf16* xp, float** acts, __bf16** actp,
+                             int i, int M) {
+    const bool last = i == net.depth - 1;
+    SplitGemmParams g{};
+    g.np = np;
+    g.A = i == 0 ? xp : actp[i - 1];
+    g.lda = i == 0 ? net.xld : net.ald;
+    g.pA = i == 0 ? net.arows * net.xld : net.aps();
+    g.sA = i == 0 ? 0 : 3 * net.aps();  // the input is shared by the ensemble members
+    if (net.x3f) {
+      g.B = net.wtp[which][i];
+      g.ldb = net.wtk(i);
+      g.pB = net.wtps(i);
+      g.sB = 3 * net.wtps(i);
+      g.b_frag = net.bfrag[i] ? 1 : 0;
+    } else {
+      g.B = net.wp[which][i];
+      g.ldb = net.wld;
+      g.pB = net.kps(i);
+      g.sB = 3 * net.kps(i);
+      g.b_kmajor = 1;
+    }
+    if (last || !net.x3f) {  // the heads read fp32
+      g.C = acts[i];
+      g.ldc = net.width;
+      g.sC = (long long)M * net.width;
+    }
+    if (!last) {  // the next layer reads the planes (x3f: so does the data grad's ReLU mask)
+      g.Cp = actp[i];
+      g.ldcp = net.ald;
+      g.pC = net.aps();
+      g.sCp = 3 * net.aps();
+    }
+    g.bias = params + net.off_b[i];
+    g.sBias = net.ms_b;
+    g.M = M;
+    g.N = net.width;
+    g.K = (int)net.wtk(i);
+    g.tag = i == 0 ? 1 : 0;
+    g.splits = -1;  // split-K when the row tiles do not fill the chip (task shards)
+    g.ws = ws_lane[cur_lane];
+    g.cnt = fin_cnt();
+    return g;
+  }
+
+  // Data grad of layer i over M rows (EPI_RELU_MASK): dz[i-1] = (dz[i] . W_i^T) * [acts[i-1] > 0], NT on
+  // planes (W_i's planes read as [N = in][K = out]).
+  // want_db: the weight grad of layer i - 1 follows (the trunk backward), so dz[i-1]'s bias-grad column
+  // sums are wanted; without it (the actor step's pass through the critic) only the data flows on.
+  // Where dz[i-1] has planes its fp32 copy would only feed those column sums: one gemm_x3f (or
+  // gemm_x3s) pass writes the planes and the sums' partials into net.dbp[i-1], and *db_chunks (set
+  // only then) is the number of row chunks it leaves, 0 when neither kernel takes that form.
+  // ragged: the launch over the members' active rows (gemm_x3f_ragged: dz[i]'s planes are compacted,
+  // so are the outputs); needs split2h, net.x3f, no want_db, and gemm_x3f_ragged_ok of the result.
+  SplitGemmParams dgrad_params(Net& net, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i, int M,
+                               bool want_db, bool ragged = false, int* db_chunks = nullptr) {
+    SplitGemmParams g{};
+    g.np = np;
+    g.A = dzp[i];
+    g.lda = net.ald;
+    g.pA = net.aps();
+    g.sA = 3 * net.aps();
+    g.B = net.wp[0][i];
+    g.ldb = net.wld;
+    g.pB = net.wps();
+    g.sB = 3 * net.wps();
+    g.b_frag = net.bfrag[i] ? 1 : 0;
+    g.C = dz[i - 1];
+    g.ldc = net.width;
+    g.sC = (long long)M * net.width;
+    if (net.x3f) {  // hidden activations keep planes only: h > 0 <=> its bf16 high plane > 0
+      g.mask16 = actp[i - 1];
+      g.ldm = (int)net.ald;
+      g.sMask = 3 * net.aps();
+    } else {
+      g.mask = acts[i - 1];
+      g.ldm = net.width;
+      g.sMask = (long long)M * net.width;
+    }
+    g.pMask = net.aps();
+    if (dzp[i - 1] && (i - 1 >= 1 || want_db)) {  // dz[0]'s planes feed only its weight grad
+      g.Cp = dzp[i - 1];
+      g.ldcp = net.ald;
+      g.pC = net.aps();
+      g.sCp = 3 * net.aps();
+    }
+    g.M = M;
+    g.N = net.width;
+    g.K = (int)net.ald;
+    g.splits = -1;
+    g.ws = ws_lane[cur_lane];
+    g.cnt = fin_cnt();
+    if (ragged) {
+      g.rag_n = act_n;
+      g.rag_rows = act_rows;
+      g.rag_ld = M;
+    }
+    if (g.Cp && !want_db) {
+      g.C = nullptr;
+    } else if (g.Cp) {
+      SplitGemmParams q = g;
+      q.C = nullptr;
+      q.dbp = net.dbp[i - 1];
+      const bool fx = gemm_x3f_ok(q, EPI_RELU_MASK, net.E);
+      const bool fs = !fx && !gemm_x3f_ok(g, EPI_RELU_MASK, net.E) && gemm_x3s_ok(q, EPI_RELU_MASK, net.E);
+      if (fx || fs) g = q;
+      const int bm = fx ? gemm_x3f_out_bm(q, EPI_RELU_MASK, net.E) : 16 * gemm_x3s_ti(M, net.width, net.E);
+      if (db_chunks) *db_chunks = (fx || fs) ? (M + bm - 1) / bm : 0;
+    }
+    return g;
+  }
+
+  // Weight grad of layer i (EPI_STORE): dW_i = in_i^T dz[i], TN on k-major planes over the krows s rows
+  // (dz is zero past B; the actor's s' rows follow at krows).  One GPU: the finish (split-K slab sums,
+  // bias grad) is deferred to the network's optimizer and the slabs wait in ws_wg[i] (null: this weight
+  // grad never splits).  Where dz[i]'s producer left column sums (dbp_chunks[i] > 0) the GEMM's finish
+  // makes the bias grad from them (cs_part set); else the caller runs colsum on the fp32 dz[i].
+  SplitGemmParams wgrad_params(Net& net, const __bf16* xp, __bf16** actp, __bf16** dzp, int i) {
+    SplitGemmParams g{};
+    g.np = np;
+    g.A = i == 0 ? xp : actp[i - 1];
+    g.lda = i == 0 ? net.xld : net.ald;
+    g.pA = i == 0 ? net.arows * net.xld : net.aps();
+    g.sA = i == 0 ? 0 : 3 * net.aps();
+    g.a_kmajor = 1;
+    g.B = dzp[i];
+    g.ldb = net.ald;
+    g.pB = net.aps();
+    g.sB = 3 * net.aps();
+    g.b_kmajor = 1;
+    g.C = net.g + net.off_W[i];
+    g.ldc = net.width;
+    g.sC = net.ms_W[i];
+    g.M = i == 0 ? net.in_dim : net.width;
+    g.N = net.width;
+    g.K = (int)net.krows;
+    g.tag = i == 0 ? 1 : 0;
+    g.splits = -1;  // by tile count (gemm_x3p_splits); the workspaces are sized for it
+    g.ws = ws_lane[cur_lane];
+    g.cnt = fin_cnt();
+    if (defer_finish()) {  // the finish runs at the start of optimize(net)
+      g.ws = net.ws_wg[i];
+      g.cnt = nullptr;
+      g.defer = &net.fin_sink;
+    }
+    if (net.dbp_chunks[i] > 0) {  // gemm_x3p finishes the bias grad (in its split-K reduce launch when it has one)
+      g.cs_part = net.dbp[i];
+      g.cs_chunks = net.dbp_chunks[i];
+      g.cs_db = net.g + net.off_b[i];
+      g.cs_sdb = net.ms_b;
+    }
+    return g;
+  }
+
   // ------------------------------------------------------------ trunk passes
   // acts[i] = relu(in_i @ W_i + b_i) for every member (batched over the ensemble)
   // which: 0 / 1 = params is Net::p / Net::tgt (their transposed copies or planes are current),
@@ -782,75 +891,8 @@ struct mtsac_engine {
     __bf16* xp = pl ? in_planes(X) : nullptr;
     for (int i = 0; i < net.depth; ++i) {
       const bool last = i == net.depth - 1;
-      if (pl && net.x3f && (i > 0 || xp)) {  // on planes, both row-major: in_i . (W_i^T)^T (gemm_x3f)
-        SplitGemmParams g{};
-        g.np = np;
-        g.A = i == 0 ? xp : actp[i - 1];
-        g.lda = i == 0 ? net.xld : net.ald;
-        g.pA = i == 0 ? net.arows * net.xld : net.aps();
-        g.sA = i == 0 ? 0 : 3 * net.aps();  // the input is shared by the ensemble members
-        g.B = net.wtp[which][i];
-        g.ldb = net.wtk(i);
-        g.pB = net.wtps(i);
-        g.sB = 3 * net.wtps(i);
-        g.b_frag = net.bfrag[i] ? 1 : 0;
-        if (last) {  // the heads read fp32
-          g.C = acts[i];
-          g.ldc = net.width;
-          g.sC = (long long)M * net.width;
-        } else {  // the next layer and the data grad's ReLU mask read the planes only
-          g.Cp = actp[i];
-          g.ldcp = net.ald;
-          g.pC = net.aps();
-          g.sCp = 3 * net.aps();
-        }
-        g.bias = params + net.off_b[i];
-        g.sBias = net.ms_b;
-        g.M = M;
-        g.N = net.width;
-        g.K = (int)net.wtk(i);
-        g.tag = i == 0 ? 1 : 0;
-        g.splits = -1;  // split-K when the row tiles do not fill the chip (task shards)
-        g.ws = ws_lane[cur_lane];
-        g.cnt = fin_cnt();
-        if (h2) {
-          RecRef* ar = act_rec(actp);
-          h2_gemm(g, i == 0 ? &r_in[inset_cur] : &ar[i - 1], &w_rec(net, which), last ? nullptr : &ar[i],
-                  (float)(i == 0 ? net.in_dim : net.width), true);
-        }
-        gemmp(g, EPI_BIAS_RELU, net.E, i == 0 ? MTSAC_FAM_INPUT_FORWARD : MTSAC_FAM_FORWARD);
-        continue;
-      }
-      if (pl && (i > 0 || xp)) {  // on planes: input (row-major) . W_i (k-major)
-        SplitGemmParams g{};
-        g.np = np;
-        g.A = i == 0 ? xp : actp[i - 1];
-        g.lda = i == 0 ? net.xld : net.ald;
-        g.pA = i == 0 ? net.arows * net.xld : net.aps();
-        g.sA = i == 0 ? 0 : 3 * net.aps();
-        g.B = net.wp[which][i];
-        g.ldb = net.wld;
-        g.pB = net.kps(i);
-        g.sB = 3 * net.kps(i);
-        g.b_kmajor = 1;
-        g.C = acts[i];
-        g.ldc = net.width;
-        g.sC = (long long)M * net.width;
-        g.bias = params + net.off_b[i];
-        g.sBias = net.ms_b;
-        if (!last) {
-          g.Cp = actp[i];
-          g.ldcp = net.ald;
-          g.pC = net.aps();
-          g.sCp = 3 * net.aps();
-        }
-        g.M = M;
-        g.N = net.width;
-        g.K = (int)(i == 0 ? net.xld : net.ald);
-        g.tag = i == 0 ? 1 : 0;
-        g.splits = -1;
-        g.ws = ws_lane[cur_lane];
-        g.cnt = fin_cnt();
+      if (pl && (i > 0 || xp)) {  // on planes
+        SplitGemmParams g = fwd_params(net, params, which, xp, acts, actp, i, M);
         if (h2) {
           RecRef* ar = act_rec(actp);
           h2_gemm(g, i == 0 ? &r_in[inset_cur] : &ar[i - 1], &w_rec(net, which), last ? nullptr : &ar[i],
@@ -946,42 +988,10 @@ struct mtsac_engine {
                    int M) {
     const __bf16* xp = (planes && i == 0) ? in_planes(X) : nullptr;
     if (planes && (i > 0 || xp) && actp && dzp && dzp[i]) {  // TN on k-major planes; bias grad by column sums
-      SplitGemmParams g{};
-      g.np = np;
-      g.A = i == 0 ? xp : actp[i - 1];
-      g.lda = i == 0 ? net.xld : net.ald;
-      g.pA = i == 0 ? net.arows * net.xld : net.aps();
-      g.sA = i == 0 ? 0 : 3 * net.aps();
-      g.a_kmajor = 1;
-      g.B = dzp[i];
-      g.ldb = net.ald;
-      g.pB = net.aps();
-      g.sB = 3 * net.aps();
-      g.b_kmajor = 1;
-      g.C = net.g + net.off_W[i];
-      g.ldc = net.width;
-      g.sC = net.ms_W[i];
-      g.M = i == 0 ? net.in_dim : net.width;
-      g.N = net.width;
-      g.K = (int)net.krows;  // the s rows (dz is zero past B; the actor's s' rows follow at krows)
-      g.tag = i == 0 ? 1 : 0;
-      g.splits = -1;  // by tile count (gemm_x3p_splits); the lane workspace is sized for it
-      g.ws = ws_lane[cur_lane];
-      g.cnt = fin_cnt();
-      if (defer_finish()) {  // the finish runs at the start of optimize(net); the slabs wait in ws_wg[i]
-        g.ws = net.ws_wg[i];  // (null: this weight grad never splits)
-        g.cnt = nullptr;
-        g.defer = &net.fin_sink;
-      }
-      if (net.dbp_chunks[i] > 0) {  // dz[i]'s producer left its column sums: gemm_x3p finishes the bias
-        g.cs_part = net.dbp[i];     // grad (in its split-K reduce launch when it has one)
-        g.cs_chunks = net.dbp_chunks[i];
-        g.cs_db = net.g + net.off_b[i];
-        g.cs_sdb = net.ms_b;
-      }
+      SplitGemmParams g = wgrad_params(net, xp, actp, dzp, i);
       if (h2) h2_gemm(g, i == 0 ? &r_in[inset_cur] : &act_rec(actp)[i - 1], &dz_rec(dzp)[i], nullptr, (float)g.K, false);
       gemmp(g, EPI_STORE, net.E, i == 0 ? MTSAC_FAM_INPUT_WEIGHT_GRAD : MTSAC_FAM_WEIGHT_GRAD);
-      if (net.dbp_chunks[i] <= 0)
+      if (net.dbp_chunks[i] <= 0)  // no column sums came with dz[i]
         colsum(dz[i], M, net.width, net.width, (long long)M * net.width, net.E, cs_part, net.g + net.off_b[i],
                net.ms_b, cur);
       return;
@@ -1006,93 +1016,23 @@ struct mtsac_engine {
     gemm(g, GEMM_TN, EPI_STORE, net.E, i == 0 ? MTSAC_FAM_INPUT_WEIGHT_GRAD : MTSAC_FAM_WEIGHT_GRAD);
   }
 
-  // want_db: the weight grad of layer i - 1 follows (the trunk backward), so dz[i-1]'s bias-grad
-  // column sums are wanted; without it (the actor step's pass through the critic) only the data
-  // flows on.  Hidden layers on gemm_x3f keep planes only: their bias grad comes from the
-  // epilogue's column sums.
-  // rag: 0 the dense launch; 1 the launch over the members' active rows (gemm_x3f_ragged: dz[i]'s planes
-  // are compacted, so are the outputs); 2 launches nothing and returns whether 1 may be used here
-  bool dgrad_layer(Net& net, const float* params, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
-                   int M, bool want_db = true, int rag = 0) {
-    if (rag != 0 && !(planes && dzp && h2 && net.x3f && !want_db)) return false;
-    if (planes && dzp) {  // NT on planes: dz[i] . W_i^T, W_i planes read as [N = in][K = out]
-      SplitGemmParams g{};
-      g.np = np;
-      g.A = dzp[i];
-      g.lda = net.ald;
-      g.pA = net.aps();
-      g.sA = 3 * net.aps();
-      g.B = net.wp[0][i];
-      g.ldb = net.wld;
-      g.pB = net.wps();
-      g.sB = 3 * net.wps();
-      g.b_frag = net.bfrag[i] ? 1 : 0;
-      g.C = dz[i - 1];
-      g.ldc = net.width;
-      g.sC = (long long)M * net.width;
-      if (net.x3f) {  // hidden activations keep planes only: h > 0 <=> its bf16 high plane > 0
-        g.mask16 = actp[i - 1];
-        g.ldm = (int)net.ald;
-        g.sMask = 3 * net.aps();
-      } else {
-        g.mask = acts[i - 1];
-        g.ldm = net.width;
-        g.sMask = (long long)M * net.width;
-      }
-      if (dzp[i - 1] && (i - 1 >= 1 || want_db)) {  // dz[0]'s planes feed only its weight grad
-        g.Cp = dzp[i - 1];
-        g.ldcp = net.ald;
-        g.pC = net.aps();
-        g.sCp = 3 * net.aps();
-      }
-      g.M = M;
-      g.N = net.width;
-      g.K = (int)net.ald;
-      g.splits = -1;
-      g.ws = ws_lane[cur_lane];
-      g.cnt = fin_cnt();
-      g.pMask = net.aps();
-      if (rag == 2) {  // the probe leaves the records alone
-        if (g.Cp) g.C = nullptr;
-        return gemm_x3f_ragged_ok(g, EPI_RELU_MASK, net.E);
-      }
+  // want_db, ragged: see dgrad_params (ragged only where actor_compact holds)
+  void dgrad_layer(Net& net, const float* params, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
+                   int M, bool want_db = true, bool ragged = false) {
+    if (planes && dzp) {
+      SplitGemmParams g = dgrad_params(net, acts, actp, dz, dzp, i, M, want_db, ragged, &net.dbp_chunks[i - 1]);
       if (h2) h2_gemm(g, &dz_rec(dzp)[i], &w_rec(net, 0), g.Cp ? &dz_rec(dzp)[i - 1] : nullptr, (float)net.width, false);
-      if (rag == 1) {
-        if (g.Cp) g.C = nullptr;
-        g.rag_n = act_n;
-        g.rag_rows = act_rows;
-        g.rag_ld = M;
+      if (ragged) {
         // the members' active rows add up to M (more only on exact ties): M rows of products, not E M
-        t_begin(MTSAC_FAM_DATA_GRAD, 2.0 * (double)g.M * g.N * g.K);
-        if (timing) {
-          tl[tl_next].M = g.M;
-          tl[tl_next].N = g.N;
-          tl[tl_next].K = g.K;
-          tl[tl_next].batch = 1;
-        }
+        t_begin(MTSAC_FAM_DATA_GRAD, g.M, g.N, g.K, 1);
         gemm_x3f_ragged(g, cur);
         fam_kernel[MTSAC_FAM_DATA_GRAD] = std::string("gemm_x3f_kernel<208, 2, ") + (g.C ? "true" : "false") + ", " +
                                           (g.Cp ? "true" : "false") + ", true, 16, 2>";
         t_end();
-        return true;
-      }
-      if (g.Cp) {  // dz[i-1]'s fp32 copy only feeds the bias grad's column sums
-        if (!want_db) {
-          g.C = nullptr;
-        } else {  // one gemm_x3f pass (no split-K) writes the planes and the column sums
-          SplitGemmParams q = g;
-          q.C = nullptr;
-          q.dbp = net.dbp[i - 1];
-          // (or gemm_x3s, the same partials over its 16 TI-row tiles)
-          const bool fx = gemm_x3f_ok(q, EPI_RELU_MASK, net.E);
-          const bool fs = !fx && !gemm_x3f_ok(g, EPI_RELU_MASK, net.E) && gemm_x3s_ok(q, EPI_RELU_MASK, net.E);
-          if (fx || fs) g = q;
-          const int bm = fx ? gemm_x3f_out_bm(q, EPI_RELU_MASK, net.E) : 16 * gemm_x3s_ti(M, net.width, net.E);
-          net.dbp_chunks[i - 1] = (fx || fs) ? (M + bm - 1) / bm : 0;
-        }
+        return;
       }
       gemmp(g, EPI_RELU_MASK, net.E, MTSAC_FAM_DATA_GRAD);
-      return true;
+      return;
     }
     GemmParams g{};
     g.A = dz[i];
@@ -1111,18 +1051,18 @@ struct mtsac_engine {
     g.N = net.width;
     g.K = net.width;
     gemm(g, GEMM_NT, EPI_RELU_MASK, net.E, MTSAC_FAM_DATA_GRAD);
-    return true;
   }
 
   // the actor step's pass through the critic runs compacted: split2h planes, two members, hidden layers,
   // and every data grad of the pass would be the plain unsplit gemm_x3f launch (task shards on split-K,
   // gemm_x3s / gemm_x3p shapes and the other precisions keep the dense pass)
   bool actor_compact(int M) {
-    if (actor_dense || !h2 || !planes || critic.E != 2 || critic.hd != 1 || critic.depth < 2 || critic.width % 4 != 0 ||
-        top_planes_ptr(critic, dzcp) == nullptr)
+    if (actor_dense || !h2 || !planes || !critic.x3f || critic.E != 2 || critic.hd != 1 || critic.depth < 2 ||
+        critic.width % 4 != 0 || top_planes_ptr(critic, dzcp) == nullptr)
       return false;
     for (int i = critic.depth - 1; i > 0; --i)
-      if (!dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, M, false, 2)) return false;
+      if (!gemm_x3f_ragged_ok(dgrad_params(critic, hc, hcp, dzc, dzcp, i, M, false, true), EPI_RELU_MASK, critic.E))
+        return false;
     return true;
   }
   __bf16* top_planes_ptr(Net& net, __bf16** dzp) const { return planes && net.depth > 1 ? dzp[net.depth - 1] : nullptr; }
@@ -1575,6 +1515,75 @@ struct mtsac_engine {
     inp[0].p = inset[k].xap;
   }
 
+  // ---- the head / loss kernels' parameter blocks, shared by step() and the per-task gradient passes
+  // what every policy-head and critic-head launch of a pass has in common, over the current row lists
+  // (counts, rows); max_count: the most rows a task holds in them; ap_ps / ap_ld: plane and row stride of
+  // the critic input planes the policy heads also write their actions to (0: fp32 only)
+  void head_base(PolicyParams& pp, CriticHeadParams& ch, int max_count, long long ap_ps, int ap_ld) {
+    pp = PolicyParams{};
+    pp.seed = cfg.noise_seed;
+    pp.counter = counter;
+    pp.A = A;
+    pp.ls_min = cfg.log_std_min;
+    pp.ls_max = cfg.log_std_max;
+    pp.ld_a_out = ld_c;
+    pp.ap_ps = ap_ps;
+    pp.ap_ld = ap_ld;
+    pp.counts = counts;
+    pp.rows = rows;
+    pp.max_rows = B;
+    pp.T_l = T_l;
+    pp.max_count = max_count;
+    ch = CriticHeadParams{};
+    ch.rew = rew;
+    ch.done = done;
+    ch.log_alpha = log_alpha;
+    ch.task = task;
+    ch.task_begin = cfg.task_begin;
+    ch.tw = cfg.use_task_weights ? tw : nullptr;
+    ch.gamma = cfg.gamma;
+    ch.clip = cfg.clip;
+    ch.T_glob = T_g;
+  }
+  // a ~ pi(.|s) from the actor's top activations h into xc_pi's action columns, with the cache the actor
+  // backward reads; a' ~ pi(.|s') into xc_next's.  The caller sets stream_id, noise_div, a_planes, ap_rec.
+  PolicyParams pi_s(const PolicyParams& pp, const float* h, bool device_noise) {
+    PolicyParams q = pp;
+    q.head = head(actor, actor.p, h, B, task);
+    q.eps = device_noise ? nullptr : eps_c;
+    q.a_out = xcp;
+    q.logpi = logpi;
+    q.cache = cache;
+    return q;
+  }
+  PolicyParams pi_next(const PolicyParams& pp, const float* h, bool device_noise) {
+    PolicyParams q = pp;
+    q.head = head(actor, actor.p, h, B, task);
+    q.eps = device_noise ? nullptr : eps_n;
+    q.a_out = xcn;
+    q.logpi = logpi_n;
+    return q;
+  }
+  // dz[0] of the critic into the policy output's gradient; the caller sets the ragged slots, the split2h
+  // record and the PCGrad explore fields
+  ActionGradParams action_grad_params() {
+    ActionGradParams ag{};
+    ag.dz1 = dzc[0];
+    ag.W0 = critic.p + critic.off_W[0];
+    ag.s_dz = (long long)B * critic.width;
+    ag.s_W0 = critic.ms_W[0];
+    ag.E = critic.E;
+    ag.B = B;
+    ag.Wc = critic.width;
+    ag.A = A;
+    ag.cache = cache;
+    ag.alpha_w = alpha_w;
+    ag.ls_min = cfg.log_std_min;
+    ag.ls_max = cfg.log_std_max;
+    ag.dout = dout_a;
+    return ag;
+  }
+
   // pipelined: eager issue that overlaps the previous step's tail (see InSet); join: the main
   // stream waits for every lane at the end (the last step of a call, and every non-pipelined one)
   void step(bool device_batch, bool device_noise, bool pipelined = false, bool join = true) {
@@ -1592,31 +1601,10 @@ struct mtsac_engine {
     actor.fin_sink.n = critic.fin_sink.n = 0;  // (a step cut short never leaves deferred finishes behind)
     zstep[0] = zero_ok(actor);
     zstep[1] = zero_ok(critic);
-    const float* twp = cfg.use_task_weights ? tw : nullptr;
-    PolicyParams pp{};
-    pp.seed = cfg.noise_seed;
-    pp.counter = counter;
-    pp.A = A;
-    pp.ls_min = cfg.log_std_min;
-    pp.ls_max = cfg.log_std_max;
-    pp.ld_a_out = ld_c;
-    pp.ap_ps = critic.arows * critic.xld;
-    pp.ap_ld = (int)critic.xld;
-    pp.counts = counts;
-    pp.rows = rows;
-    pp.max_rows = Bl;
-    pp.T_l = T_l;
-    pp.max_count = device_batch ? n : Bl;  // replay batches hold exactly n rows per task
-    CriticHeadParams ch{};
-    ch.rew = rew;
-    ch.done = done;
-    ch.log_alpha = log_alpha;
-    ch.task = task;
-    ch.task_begin = cfg.task_begin;
-    ch.tw = twp;
-    ch.gamma = cfg.gamma;
-    ch.clip = cfg.clip;
-    ch.T_glob = T_g;
+    PolicyParams pp;
+    CriticHeadParams ch;
+    // replay batches hold exactly n rows per task
+    head_base(pp, ch, device_batch ? n : Bl, critic.arows * critic.xld, (int)critic.xld);
 
     if (overlap) {  // the gather and critic(s, a) reuse buffers step k's actor-loss pass reads
       hipStream_t w = p2 ? s2 : st;
@@ -1652,50 +1640,23 @@ struct mtsac_engine {
     // per step at 300 GB/s)
     const bool split_af = split_actor_req > 0 || (split_actor_req < 0 && dev_collective() && one_stream && !build &&
                                                   !timing_serial && !lanes_alt && Bl <= 2048);
-    auto pi_s = [&](PolicyParams& q) {  // pi(s): the actor-loss half of the policy heads
-      q = pp;
-      q.head = head(actor, actor.p, ha[actor.depth - 1], Bl, task);
-      q.eps = device_noise ? nullptr : eps_c;
-      q.stream_id = 2;
-      q.a_out = xcp;
-      q.a_planes = in_planes(xcp);
+    // the step's two policy-head halves: the noise streams 2 (a) and 1 (a'), the actions into the
+    // critic input planes as well, under the input planes' record
+    auto step_pi = [&](bool next) {
+      PolicyParams q = next ? pi_next(pp, han[actor.depth - 1], device_noise) : pi_s(pp, ha[actor.depth - 1], device_noise);
+      q.stream_id = next ? 1 : 2;
+      q.a_planes = in_planes(next ? xcn : xcp);
       q.ap_rec = h2 ? r_in[inset_cur].d : nullptr;
-      q.logpi = logpi;
-      q.cache = cache;
+      return q;
     };
     const int s_af = seg({s_in}, ol ? 0 : 2, [&] {
       if (split_af) {  // the s' rows only: a' ~ pi(.|s') for the TD target
         trunk_forward(actor, actor.p, 0, xan, ld_a, han, hap_s2, Bl);
-        PolicyParams qn = pp;
-        qn.head = head(actor, actor.p, han[actor.depth - 1], Bl, task);
-        qn.eps = device_noise ? nullptr : eps_n;
-        qn.stream_id = 1;
-        qn.a_out = xcn;
-        qn.a_planes = in_planes(xcn);
-        qn.ap_rec = h2 ? r_in[inset_cur].d : nullptr;
-        qn.logpi = logpi_n;
-        policy_head(qn, cur);
+        policy_head(step_pi(true), cur);
         return;
       }
       trunk_forward(actor, actor.p, 0, xa, ld_a, ha, hap, Ma);
-      PolicyParams q = pp;
-      q.head = head(actor, actor.p, ha[actor.depth - 1], Bl, task);
-      q.eps = device_noise ? nullptr : eps_c;
-      q.stream_id = 2;
-      q.a_out = xcp;
-      q.a_planes = in_planes(xcp);
-      q.ap_rec = h2 ? r_in[inset_cur].d : nullptr;
-      q.logpi = logpi;
-      q.cache = cache;
-      PolicyParams qn = pp;
-      qn.head = head(actor, actor.p, han[actor.depth - 1], Bl, task);
-      qn.eps = device_noise ? nullptr : eps_n;
-      qn.stream_id = 1;
-      qn.a_out = xcn;
-      qn.a_planes = in_planes(xcn);
-      qn.ap_rec = q.ap_rec;
-      qn.logpi = logpi_n;
-      policy_head_pair(q, qn, cur);
+      policy_head_pair(step_pi(false), step_pi(true), cur);
       if (snap_on)
         (void)hipMemcpyAsync(dbg_snap[0], ha[actor.depth - 1], sizeof(float) * Ma * actor.width,
                              hipMemcpyDeviceToDevice, cur);
@@ -1752,9 +1713,7 @@ struct mtsac_engine {
       if (split_af)  // the s rows beside the critic's all-reduce
         s_afs = seg({s_in}, 1, [&] {
           trunk_forward(actor, actor.p, 0, xa, ld_a, ha, hap, Bl);
-          PolicyParams q;
-          pi_s(q);
-          policy_head(q, cur);
+          policy_head(step_pi(false), cur);
         });
     });
     // reduce over shards, clip + Adam + Polyak (mtsac.py:599-613)
@@ -1786,22 +1745,9 @@ struct mtsac_engine {
       if (rag) active_rows(dq, critic.E, Bl, act_n, act_rows, act_slot, cur);
       head_bwd(critic, c.head, dq, Bl, dzc, dzcp, false, rag ? act_slot : nullptr);
       for (int i = critic.depth - 1; i > 0; --i)
-        dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, Bl, false, rag ? 1 : 0);
-      ActionGradParams ag{};
-      ag.dz1 = dzc[0];
+        dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, Bl, false, rag);
+      ActionGradParams ag = action_grad_params();
       ag.slot = rag ? act_slot : nullptr;
-      ag.W0 = critic.p + critic.off_W[0];
-      ag.s_dz = (long long)Bl * critic.width;
-      ag.s_W0 = critic.ms_W[0];
-      ag.E = critic.E;
-      ag.B = Bl;
-      ag.Wc = critic.width;
-      ag.A = A;
-      ag.cache = cache;
-      ag.alpha_w = alpha_w;
-      ag.ls_min = cfg.log_std_min;
-      ag.ls_max = cfg.log_std_max;
-      ag.dout = dout_a;
       if (h2) {
         ag.dout_rec = r_dout.d;
         ag.dout_parts = &r_dout.n;
@@ -1956,32 +1902,6 @@ struct mtsac_engine {
     if (cfg.use_task_weights) row_alpha(task, cfg.task_begin, log_alpha, T_g, Bl, 1, row_c, tw, cur);
   }
 
-  void tg_params(PolicyParams& pp, CriticHeadParams& ch) {
-    const int Bl = B, n_rows = B / T_l;
-    pp = PolicyParams{};
-    pp.seed = cfg.noise_seed;
-    pp.counter = counter;
-    pp.A = A;
-    pp.ls_min = cfg.log_std_min;
-    pp.ls_max = cfg.log_std_max;
-    pp.ld_a_out = ld_c;
-    pp.counts = counts;
-    pp.rows = rows;
-    pp.max_rows = Bl;
-    pp.T_l = T_l;
-    pp.max_count = n_rows;
-    ch = CriticHeadParams{};
-    ch.rew = rew;
-    ch.done = done;
-    ch.log_alpha = log_alpha;
-    ch.task = task;
-    ch.task_begin = cfg.task_begin;
-    ch.tw = cfg.use_task_weights ? tw : nullptr;
-    ch.gamma = cfg.gamma;
-    ch.clip = cfg.clip;
-    ch.T_glob = T_g;
-  }
-
   void task_grads(bool device_batch, bool device_noise) {
     tg_prepare(device_batch);
     for (int w = 0; w < 2; ++w) (void)hipMemsetAsync(tg[w], 0, sizeof(float) * T_l * tgP[w], cur);
@@ -1995,19 +1915,15 @@ struct mtsac_engine {
     const int Bl = B, n_rows = B / T_l;
     PolicyParams pp;
     CriticHeadParams ch;
-    tg_params(pp, ch);
+    head_base(pp, ch, n_rows, 0, 0);  // fp32 operands: no action planes
     const int Dc = critic.depth, Da = actor.depth;
 
     // ---- critic (mtsac.py:1000-1048): a_n ~ pi(.|s), y from the target critic at (s', a_n)
     trunk_forward(actor, actor.p, 0, xa, ld_a, han, nullptr, Bl);
     {
-      PolicyParams q = pp;
-      q.head = head(actor, actor.p, han[Da - 1], Bl, task);
-      q.eps = device_noise ? nullptr : eps_n;
+      PolicyParams q = pi_next(pp, han[Da - 1], device_noise);
       q.stream_id = pc ? 5 : 3;
       q.noise_div = pc ? T_l : 0;
-      q.a_out = xcn;
-      q.logpi = logpi_n;
       policy_head(q, cur);
     }
     trunk_forward(critic, critic.tgt, 1, xcn, ld_c, hct, nullptr, Bl);
@@ -2046,19 +1962,14 @@ struct mtsac_engine {
     const int Bl = B, n_rows = B / T_l;
     PolicyParams pp;
     CriticHeadParams ch;
-    tg_params(pp, ch);
+    head_base(pp, ch, n_rows, 0, 0);
     const int Dc = critic.depth, Da = actor.depth;
     // ---- actor (mtsac.py:1051-1090): the current critic, per-task mean over n rows
     trunk_forward(actor, actor.p, 0, xa, ld_a, ha, nullptr, Bl);
     {
-      PolicyParams q = pp;
-      q.head = head(actor, actor.p, ha[Da - 1], Bl, task);
-      q.eps = device_noise ? nullptr : eps_c;
+      PolicyParams q = pi_s(pp, ha[Da - 1], device_noise);
       q.stream_id = pc ? 6 : 4;
       q.noise_div = pc ? T_l : 0;
-      q.a_out = xcp;
-      q.logpi = logpi;
-      q.cache = cache;
       policy_head(q, cur);
     }
     trunk_forward(critic, critic.p, 0, xcp, ld_c, hc, nullptr, Bl);
@@ -2076,20 +1987,7 @@ struct mtsac_engine {
     }
     for (int i = Dc - 1; i > 0; --i) dgrad_layer(critic, critic.p, hc, nullptr, dzc, nullptr, i, Bl);
     {
-      ActionGradParams ag{};
-      ag.dz1 = dzc[0];
-      ag.W0 = critic.p + critic.off_W[0];
-      ag.s_dz = (long long)Bl * critic.width;
-      ag.s_W0 = critic.ms_W[0];
-      ag.E = critic.E;
-      ag.B = Bl;
-      ag.Wc = critic.width;
-      ag.A = A;
-      ag.cache = cache;
-      ag.alpha_w = alpha_w;
-      ag.ls_min = cfg.log_std_min;
-      ag.ls_max = cfg.log_std_max;
-      ag.dout = dout_a;
+      ActionGradParams ag = action_grad_params();
       if (pc) {  // mtsac.py:668-673 with the default _explore = True of the split call (:678-682)
         ag.a_data = xc;
         ag.ld_a_data = ld_c;
@@ -2557,7 +2455,7 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
       return v ? atoi(v) : 1;
     }();
     const int bfrag_req = g_bfrag_mode >= 0 ? g_bfrag_mode : bfrag_env;
-    // candidates; frag_probe (after the workspaces) keeps those whose every trunk GEMM is gemm_x3f's
+    // candidates; frag_probe (once the step's buffers exist) keeps those whose every trunk GEMM is gemm_x3f's
     const bool cand = net->x3f && bfrag_req != 0 && net->depth <= MAX_TILE_LEAVES && net->width % 16 == 0 &&
                       net->ald % 64 == 0 && net->wld % 32 == 0;
     for (int i = 0; i < net->depth; ++i) net->bfrag[i] = cand;
@@ -2574,37 +2472,38 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
         (rc = e->alloc(&net->whT, (size_t)e->T_l * net->width * net->hd)))
       return bad(rc);
   }
-  {  // split-K workspaces: the largest GEMM that splits, per lane
+  e->Ma = (int)(e->actor.krows + e->B);
+  {  // split-K workspaces: the largest GEMM that splits, per lane.  The plane GEMMs' shapes come from the
+     // step's builders (no buffer exists yet: their pointers are null here).  Every forward and data grad
+     // is sized for gemm_x3p and for gemm_x3f (its K in steps of 64), whichever kernel will take it.
     long long ws = 0;
-    for (Net* net : {&e->actor, &e->critic})
+    auto fd = [&](const SplitGemmParams& g, int batch) {
+      ws = std::max(ws, gemm_x3p_ws_floats(g.M, g.N, g.K, batch, false));
+      ws = std::max(ws, gemm_x3f_ws_floats(g.M, g.N, (int)align_up(g.K, 64), batch));
+    };
+    for (Net* net : {&e->actor, &e->critic}) {
+      const bool ac = net == &e->actor;
+      float **acts = ac ? e->ha : e->hc, **dz = ac ? e->dza : e->dzc;
+      __bf16 **actp = ac ? e->hap : e->hcp, **dzp = ac ? e->dzap : e->dzcp;
       for (int i = 0; i < net->depth; ++i) {
-        const int M = i == 0 ? net->in_dim : net->width;
+        const int M = i == 0 ? net->in_dim : net->width;  // the fp32 weight grad
         ws = std::max(ws, gemm_ws_floats(M, net->width, net->E, gemm_splits(M, net->width, e->B, net->E)));
-        if (e->planes) {
-          ws = std::max(ws, gemm_x3p_ws_floats(M, net->width, (int)net->krows, net->E, true));  // weight grad
-          for (int rows : {e->B, net == &e->actor ? (int)(net->krows + e->B) : e->B}) {  // data grad, forward
-            ws = std::max(ws, gemm_x3p_ws_floats(rows, net->width, (int)(i == 0 ? net->xld : net->ald), net->E, false));
-            ws = std::max(ws, gemm_x3f_ws_floats(rows, net->width,
-                                                 (int)(i == 0 ? align_up(net->in_dim, 64) : net->ald), net->E));
-          }
-        }
+        if (!e->planes) continue;
+        for (int rows : {e->B, ac ? e->Ma : e->B}) fd(e->fwd_params(*net, net->p, 0, nullptr, acts, actp, i, rows), net->E);
+        if (i > 0) fd(e->dgrad_params(*net, acts, actp, dz, dzp, i, e->B, true), net->E);
+        const SplitGemmParams wg = e->wgrad_params(*net, nullptr, actp, dzp, i);
+        const long long w = gemm_x3p_ws_floats(wg.M, wg.N, wg.K, net->E, true);
+        ws = std::max(ws, w);  // sharded (or MTSAC_DEFER_FINISH=0): its slabs go to the lane workspace
+        // the deferred finishes' slabs, per layer (Net::fin_sink); sharded runs never use them, but
+        // sharding is set after create
+        if (e->defer_finish() && w > 0 && (rc = e->alloc(&net->ws_wg[i], (size_t)w))) return bad(rc);
       }
+    }
     for (float*& w : e->ws_lane)
       if ((rc = e->alloc(&w, (size_t)std::max(ws, 1LL)))) return bad(rc);
-    if (e->planes && e->defer_finish())  // the deferred weight-grad finishes' slabs, per layer (Net::fin_sink);
-      for (Net* net : {&e->actor, &e->critic})  // not with MTSAC_DEFER_FINISH=0 (sharded runs never use them either,
-                                                 // but sharding is set after create)
-        for (int i = 0; i < net->depth; ++i) {
-          const long long w = gemm_x3p_ws_floats(i == 0 ? net->in_dim : net->width, net->width, (int)net->krows,
-                                                 net->E, true);
-          if (w > 0 && (rc = e->alloc(&net->ws_wg[i], (size_t)w))) return bad(rc);
-        }
     for (int*& c : e->cnt_lane)
       if ((rc = e->alloc(&c, (size_t)GEMM_X3F_CNT))) return bad(rc);
   }
-  for (Net* net : {&e->actor, &e->critic})
-    for (int i = 0; i < net->depth; ++i)
-      if (net->bfrag[i]) net->bfrag[i] = e->frag_probe(*net, i);
 
   const int B = e->B;
   if ((rc = e->alloc(&e->store, (size_t)c.capacity * e->T_l * e->R))) return bad(rc);
@@ -2614,7 +2513,6 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
   if ((rc = e->alloc(&e->idx, e->n))) return bad(rc);
   if ((rc = e->alloc(&e->rmin, e->T_l))) return bad(rc);
   if ((rc = e->alloc(&e->rmax, e->T_l))) return bad(rc);
-  e->Ma = (int)(e->actor.krows + B);
   for (auto& q : e->inset) {
     if ((rc = e->alloc(&q.xa, (size_t)e->Ma * e->ld_a))) return bad(rc);  // [s | pad | s'], pad rows stay 0
     if ((rc = e->alloc(&q.task, B)) || (rc = e->alloc(&q.counts, e->T_l)) || (rc = e->alloc(&q.rows, (size_t)e->T_l * B)))
@@ -2687,6 +2585,11 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
     const int wmax = std::max(c.actor_width, c.critic_width);
     if ((rc = e->alloc(&e->cs_part, (size_t)std::max(1, c.num_critics) * COLSUM_CHUNKS * wmax))) return bad(rc);
   }
+  // the fragment-layout candidates that hold (nothing before this depends on Net::bfrag: the planes are
+  // first written by set_params)
+  for (Net* net : {&e->actor, &e->critic})
+    for (int i = 0; i < net->depth; ++i)
+      if (net->bfrag[i]) net->bfrag[i] = e->frag_probe(*net, i);
   if ((rc = e->alloc(&e->dq, (size_t)c.num_critics * B))) return bad(rc);
   // the active-row lists at their worst case: every row of every member (all ties)
   if ((rc = e->alloc(&e->act_n, (size_t)std::max(2, c.num_critics)))) return bad(rc);
