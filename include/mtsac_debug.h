@@ -135,6 +135,12 @@ int mtsac_debug_set_pipeline(struct mtsac_engine* engine, int32_t on);
  * form needs MTSAC_LANES=1 and enough hardware queues: GPU_MAX_HW_QUEUES as the process started
  * >= 5 per live engine + 3), else 0. */
 int mtsac_debug_lane_mode(struct mtsac_engine* engine);
+/* The form optimize() gives one network's clip / Adam / Polyak pass (which 0 actor, 1 critic), through
+ * the predicates it uses itself: bits 0-1 the trunk kernels' form (0 elementwise only, 1 flat plane
+ * segments, 2 64x64 tiles writing natural and transposed planes); bit 4 the head pass writes the
+ * transposed head kernel (AdamParams::whT); bit 5 the network ran the sharded optimizer in the last
+ * step issued.  Tests only. */
+int mtsac_debug_opt_form(struct mtsac_engine* engine, int which);
 /* Guard zones (MTSAC_GUARD_BYTES=n in the environment before the engine is created): n bytes of 0xFF
  * around every device allocation.  Returns the number of guards a kernel wrote (0 = intact; -95 when
  * the mode is off); the first few are named in mtsac_last_error. */

@@ -173,6 +173,7 @@ SIGNATURES = {
     "mtsac_debug_drq_c51": (ctypes.c_int, [ctypes.c_int] * 4 + [P] * 8 + [ctypes.c_float] * 3 + [P] * 6),
     "mtsac_debug_set_pipeline": (ctypes.c_int, [P, I32]),
     "mtsac_debug_lane_mode": (ctypes.c_int, [P]),
+    "mtsac_debug_opt_form": (ctypes.c_int, [P, ctypes.c_int]),
     "mtsac_debug_check_guards": (ctypes.c_int, [P]),
     "mtsac_debug_snapshot": (ctypes.c_int, [P, ctypes.c_int32]),
     "mtsac_debug_read": (ctypes.c_int, [P, ctypes.c_int32, P, ctypes.c_int64]),

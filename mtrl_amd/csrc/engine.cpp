@@ -987,7 +987,11 @@ struct mtsac_engine {
   void wgrad_layer(Net& net, const float* X, int ldx, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
                    int M) {
     const __bf16* xp = (planes && i == 0) ? in_planes(X) : nullptr;
-    if (planes && (i > 0 || xp) && actp && dzp && dzp[i]) {  // TN on k-major planes; bias grad by column sums
+    // the top layer's dz planes exist only where the head backward writes them (top_planes: a trunk with
+    // hidden layers); a one-layer trunk's head backward leaves the fp32 dz[0], which the fp32-operand GEMM
+    // below reads (its dzp[0] buffer is never written: the plane GEMM on it gave dW_0 = 0)
+    const bool dz_planes = i + 1 < net.depth || top_planes_ptr(net, dzp) != nullptr;
+    if (planes && dz_planes && (i > 0 || xp) && actp && dzp && dzp[i]) {  // TN on k-major planes; bias grad by column sums
       SplitGemmParams g = wgrad_params(net, xp, actp, dzp, i);
       if (h2) h2_gemm(g, i == 0 ? &r_in[inset_cur] : &act_rec(actp)[i - 1], &dz_rec(dzp)[i], nullptr, (float)g.K, false);
       gemmp(g, EPI_STORE, net.E, i == 0 ? MTSAC_FAM_INPUT_WEIGHT_GRAD : MTSAC_FAM_WEIGHT_GRAD);
@@ -3731,6 +3735,17 @@ int mtsac_debug_read(mtsac_engine* h, int32_t id, float* dst, int64_t count) {
 int mtsac_debug_lane_mode(mtsac_engine* h) {
   if (!h) return fail(-22, "null engine");
   return h->one_stream ? 1 : 0;
+}
+
+int mtsac_debug_opt_form(mtsac_engine* h, int which) {
+  if (!h) return fail(-22, "null engine");
+  if (which != 0 && which != 1) return fail(-22, "which must be 0 (actor) or 1 (critic)");
+  const Net& net = which == 1 ? h->critic : h->actor;
+  // the order of opt_params: tiles before plane segments
+  int r = h->tiles_fusable(net) ? 2 : h->planes_fusable(net) ? 1 : 0;
+  if (h->whT_fused(net)) r |= 16;
+  if (h->zero_of(net)) r |= 32;
+  return r;
 }
 
 int mtsac_debug_timed_launch(mtsac_engine* h, int32_t i, int32_t* dims, double* ms) {

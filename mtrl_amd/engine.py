@@ -102,6 +102,12 @@ class MTSACEngine:
         check(self.lib.mtsac_get_adam_count(self._h, which, ctypes.byref(c)))
         return c.value
 
+    def opt_form(self, which: int) -> int:
+        """Form of the fused optimizer pass of the actor (0) or critic (1): bits 0-1 0 elementwise,
+        1 plane segments, 2 tiles; bit 4 transposed head kernel written; bit 5 sharded
+        (include/mtsac_debug.h mtsac_debug_opt_form)."""
+        return check(self.lib.mtsac_debug_opt_form(self._h, which))
+
     # ------------------------------------------------------------------ replay buffer
     def buffer_add(self, obs, next_obs, actions, rewards, dones) -> None:
         """Non-blocking add.  Device (torch) tensors are read in the order of torch's current
