@@ -318,6 +318,31 @@ int mtsac_task_pcgrad_solve(mtsac_engine* h, int which, const int32_t* perm, int
                             float* logs /* 6 */);
 int mtsac_task_combine(mtsac_engine* h, int which, const float* w, float* out_dense);
 
+/* ---- CAGrad (CAGradConfig on both optimizers, mtrl/config/optim.py and mtrl/optim/cagrad.py).
+ * DESIGN.md section 11.  The same split-loss step as PCGrad's with another solve between the Gram matrix
+ * and the combine: the per-task clip to norm 1, the scaling, num_iterations - 1 momentum-SGD steps on the
+ * task weights (from zeros) and a final evaluation, softmax of the best iterate, the combine weights.
+ * mtsac_set_cagrad: on = 1 makes mtsac_update / mtsac_update_many run the CAGrad step for BOTH networks.
+ * The reference's values are c = 0.5, num_iterations = 21, learning_rate = 25 (50 from 50 tasks on),
+ * momentum = 0.5.  Limits and error codes as mtsac_set_pcgrad (-95 sharded or use_task_weights, -22 above
+ * 64 tasks, -12 out of memory, eager step: mtsac_enable_graph(1) returns -95 while on); -16 while PCGrad
+ * is on (and mtsac_set_pcgrad(1) returns -16 while CAGrad is on); -22 for num_iterations < 1 or > 1024, a
+ * non-finite or negative c, a non-finite learning_rate or momentum.  Log slots 2, 5, 7 as in the PCGrad
+ * step.
+ * mtsac_get_cagrad_logs: per network (critic, then actor) the CAGradState of the last step after
+ * task_weights -- avg_grad_magnitude, avg_grad_magnitude_before_surgery, avg_cosine_similarity (NaN
+ * without cosine_sim_logs), cagrad_objective -- then the T task_weights: out[2 * (4 + T)].
+ * mtsac_task_cagrad_solve: the kernel alone, on the matrix mtsac_set_task_gradients / mtsac_task_gradients
+ * left: Gram + solve from the start w0 (NULL: zeros): w[T] (the combine weights on the raw rows, for
+ * mtsac_task_combine), task_weights[T], logs[6] (the four scalars above, the index of the best iterate,
+ * |mean_t g_t|), obj_hist[num_iterations] (the objective at every evaluated iterate, fp64). */
+int mtsac_set_cagrad(mtsac_engine* h, int32_t on, double c, int32_t num_iterations, double learning_rate,
+                     double momentum, int32_t cosine_sim_logs);
+int mtsac_get_cagrad_logs(mtsac_engine* h, float* out /* 2 * (4 + T) */);
+int mtsac_task_cagrad_solve(mtsac_engine* h, int which, double c, int32_t num_iterations, double learning_rate,
+                            double momentum, const double* w0, int32_t cosine_sim_logs, float* w,
+                            float* task_weights, float* logs /* 6 */, double* obj_hist);
+
 #ifdef __cplusplus
 }
 #endif

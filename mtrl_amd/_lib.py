@@ -154,6 +154,10 @@ SIGNATURES = {
     "mtsac_task_gram": (ctypes.c_int, [P, ctypes.c_int, P]),
     "mtsac_task_pcgrad_solve": (ctypes.c_int, [P, ctypes.c_int, P, I32, P, P]),
     "mtsac_task_combine": (ctypes.c_int, [P, ctypes.c_int, P, P]),
+    "mtsac_set_cagrad": (ctypes.c_int, [P, I32, ctypes.c_double, I32, ctypes.c_double, ctypes.c_double, I32]),
+    "mtsac_get_cagrad_logs": (ctypes.c_int, [P, P]),
+    "mtsac_task_cagrad_solve": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_double, I32, ctypes.c_double,
+                                               ctypes.c_double, P, I32, P, P, P, P]),
     "mtsac_debug_gemm_bench": (ctypes.c_int, [ctypes.c_int] * 8 + [PD]),
     "mtsac_debug_gemm_x3p": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
     "mtsac_debug_gemm_x3p_bench": (ctypes.c_int, [ctypes.c_int] * 6 + [PD]),

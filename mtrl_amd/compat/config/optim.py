@@ -2,6 +2,7 @@
 is executed by the engine's optimizer kernels (mtrl_amd/csrc/optim.hip)."""
 
 from dataclasses import dataclass
+from typing import Any
 
 from .utils import Optimizer
 
@@ -31,6 +32,24 @@ class PCGradConfig(OptimizerConfig):
 
     num_tasks: int
     cosine_sim_logs: bool = False
+
+    @property
+    def requires_split_task_losses(self) -> bool:
+        return True
+
+
+@dataclass(frozen=True, kw_only=True)
+class CAGradConfig(OptimizerConfig):
+    """config/optim.py:100-118: optax.chain(cagrad(num_tasks), clip, adam).  ``cagrad()`` is called with
+    its defaults (c = 0.5, 21 iterations, learning rate 25 below 50 tasks and 50 from there on, momentum
+    0.5, no cosine logs); ``cagrad_optimizer`` and ``initial_weights`` are fields the reference never
+    reads.  The engine runs the weight search in Gram form on the per-task gradients
+    (mtrl_amd/csrc/cagrad.hip); both the actor's and the critic's optimizer must be CAGrad."""
+
+    num_tasks: int
+    cagrad_optimizer: OptimizerConfig
+    initial_weights: Any | None = None
+    max_grad_norm: float | None = None
 
     @property
     def requires_split_task_losses(self) -> bool:

@@ -6,7 +6,8 @@ reference's functional signatures (``self, logs = self.update(data)``) while the
 lives in one ``MTSACEngine`` (device memory, mutated in place; methods return ``self``).
 Supported: multi-head MLP actor/critic (MultiHeadConfig or VanillaNetworkConfig with
 num_tasks from the algorithm config), MSE critic, Adam optimizers -- the north-star path --
-and PCGrad gradient surgery on both networks (PCGradConfig, experiments/misc/mt10_mtmhsac_pcgrad.py).
+PCGrad gradient surgery on both networks (PCGradConfig, experiments/misc/mt10_mtmhsac_pcgrad.py) and
+CAGrad on both networks (CAGradConfig, experiments/misc/mt10_mtmhsac_cagrad.py).
 """
 
 from __future__ import annotations
@@ -17,10 +18,10 @@ from collections.abc import Mapping
 import numpy as np
 
 from .... import _lib as L
-from ....engine import PCGRAD_LOG_KEYS, MTSACEngine, make_config
+from ....engine import CAGRAD_LOG_KEYS, PCGRAD_LOG_KEYS, MTSACEngine, make_config
 from ....init import init_mtsac
 from ...config.networks import ContinuousActionPolicyConfig, QValueFunctionConfig
-from ...config.optim import OptimizerConfig, PCGradConfig
+from ...config.optim import CAGradConfig, OptimizerConfig, PCGradConfig
 from ...config.rl import AlgorithmConfig
 from ...config.utils import Activation, Initializer, Optimizer
 from ..buffers import MultiTaskReplayBuffer
@@ -44,14 +45,16 @@ class MTSACConfig(AlgorithmConfig):
 class _DeviceLogs(Mapping):
     """The update's LogDict, fetched from the device on first access (like jax.device_get)."""
 
-    def __init__(self, engine: MTSACEngine, pcgrad: bool = False):
-        self._engine, self._d, self._pcgrad = engine, None, pcgrad
+    def __init__(self, engine: MTSACEngine, pcgrad: bool = False, cagrad: bool = False):
+        self._engine, self._d, self._pcgrad, self._cagrad = engine, None, pcgrad, cagrad
 
     def _get(self):
         if self._d is None:
             self._d = self._engine.logs()
             if self._pcgrad:  # the PCGradState of both optimizers (mtrl/optim/pcgrad.py:12-17)
                 self._d.update(self._engine.pcgrad_logs())
+            if self._cagrad:  # the CAGradState of both optimizers (mtrl/optim/cagrad.py:12-17)
+                self._d.update(self._engine.cagrad_logs())
         return self._d
 
     def __getitem__(self, k):
@@ -61,7 +64,8 @@ class _DeviceLogs(Mapping):
         return iter(self._get())
 
     def __len__(self):
-        return len(L.LOG_KEYS) + (2 * len(PCGRAD_LOG_KEYS) if self._pcgrad else 0)
+        return (len(L.LOG_KEYS) + (2 * len(PCGRAD_LOG_KEYS) if self._pcgrad else 0) +
+                (2 * len(CAGRAD_LOG_KEYS) if self._cagrad else 0))
 
 
 def _check_supported(net, what: str):
@@ -71,9 +75,10 @@ def _check_supported(net, what: str):
         raise NotImplementedError(f"{what}: only he_uniform trunk init is implemented")
     if not getattr(net, "use_bias", True):
         raise NotImplementedError(f"{what}: use_bias=False is not implemented")
-    split = net.optimizer.requires_split_task_losses and not isinstance(net.optimizer, PCGradConfig)
+    split = net.optimizer.requires_split_task_losses and not isinstance(net.optimizer, (PCGradConfig, CAGradConfig))
     if net.optimizer.optimizer is not Optimizer.Adam or split:
-        raise NotImplementedError(f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad")
+        raise NotImplementedError(
+            f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad or CAGrad")
 
 
 def _check_pcgrad(config: "MTSACConfig", task_shard) -> bool:
@@ -103,6 +108,31 @@ def _check_pcgrad(config: "MTSACConfig", task_shard) -> bool:
     return True
 
 
+def _check_cagrad(config: "MTSACConfig", task_shard) -> bool:
+    """True when both optimizers are CAGrad; raises for what the engine's CAGrad step does not run."""
+    opt_a = config.actor_config.network_config.optimizer
+    opt_c = config.critic_config.network_config.optimizer
+    ca, cc = isinstance(opt_a, CAGradConfig), isinstance(opt_c, CAGradConfig)
+    if not (ca or cc):
+        return False
+    if ca != cc:
+        raise NotImplementedError(
+            "CAGrad on one network only: the reference hands the critic's optimizer per-task gradients only when "
+            "the ACTOR's optimizer asks for split losses (mtsac.py:581), and cagrad's shape assert fails on "
+            "anything else; give both actor and critic a CAGradConfig")
+    if opt_a.num_tasks != config.num_tasks or opt_c.num_tasks != config.num_tasks:
+        raise ValueError("CAGradConfig.num_tasks must equal the algorithm's num_tasks")
+    if config.use_task_weights:
+        raise NotImplementedError(
+            "CAGrad with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
+            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
+    if task_shard is not None:
+        raise NotImplementedError(
+            "CAGrad on a task-sharded engine: the weight search needs every task's gradient of the whole network "
+            "on one engine (the Gram matrix couples all tasks)")
+    return True
+
+
 class MTSAC(OffPolicyAlgorithm):
     def __init__(self, config: MTSACConfig, env_config, seed: int, engine: MTSACEngine, cfg_kwargs: dict):
         self.config = config
@@ -115,6 +145,7 @@ class MTSAC(OffPolicyAlgorithm):
         self.gamma, self.tau = config.gamma, config.tau
         self.target_entropy = -float(np.prod(env_config.action_space.shape))
         self.pcgrad = False  # both optimizers PCGrad: the engine runs the gradient-surgery step
+        self.cagrad = False  # both optimizers CAGrad: the same step with CAGrad's solve
 
     # ------------------------------------------------------------------ construction
     @staticmethod
@@ -128,6 +159,7 @@ class MTSAC(OffPolicyAlgorithm):
         _check_supported(net_a, "actor")
         _check_supported(net_c, "critic")
         pcgrad = _check_pcgrad(config, task_shard)
+        cagrad = _check_cagrad(config, task_shard)
         if task_shard is not None:
             raise NotImplementedError("task sharding is driven through mtrl_amd.shard, not this trainer")
         T = config.num_tasks
@@ -148,6 +180,8 @@ class MTSAC(OffPolicyAlgorithm):
         eng = MTSACEngine(make_config(**kw), device=device)
         if pcgrad:
             eng.set_pcgrad(True, net_a.optimizer.cosine_sim_logs)
+        if cagrad:
+            eng.set_cagrad(True)  # cagrad()'s defaults, as CAGradConfig.spawn calls it
         a, q = init_mtsac(T, obs_dim, act_dim, net_a.width, net_a.depth, net_c.width, net_c.depth,
                           config.num_critics, seed=seed)
         eng.set_params(L.ACTOR, a)
@@ -157,6 +191,7 @@ class MTSAC(OffPolicyAlgorithm):
         print("Critic Params:", eng.param_count(L.CRITIC))
         agent = MTSAC(config, env_config, seed, eng, kw)
         agent.pcgrad = pcgrad
+        agent.cagrad = cagrad
         return agent
 
     def _rebuild(self, **changes) -> None:
@@ -175,6 +210,8 @@ class MTSAC(OffPolicyAlgorithm):
         old.close()
         if self.pcgrad:
             self.engine.set_pcgrad(True, self.config.actor_config.network_config.optimizer.cosine_sim_logs)
+        if self.cagrad:
+            self.engine.set_cagrad(True)
         for w, v in keep.items():
             self.engine.set_params(w, v)
         for i, c in enumerate(counts):
@@ -231,13 +268,13 @@ class MTSAC(OffPolicyAlgorithm):
         if n != self._cfg_kwargs["batch_per_task"]:  # raises once a buffer lives in the engine
             self._rebuild(batch_per_task=n, capacity=max(self._cfg_kwargs["capacity"], n))
         self.engine.update(tuple(data))
-        return self, _DeviceLogs(self.engine, self.pcgrad)
+        return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad)
 
     def update_from_buffer(self, replay_buffer, batch_size: int, want_logs: bool):
         if getattr(replay_buffer, "engine", None) is self.engine and batch_size // self.num_tasks == \
                 self._cfg_kwargs["batch_per_task"]:
             self.engine.update_many(1)  # device sampling + update, no host round trip
-            return self, _DeviceLogs(self.engine, self.pcgrad)
+            return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad)
         return super().update_from_buffer(replay_buffer, batch_size, want_logs)
 
     def compute_weights(self, data):

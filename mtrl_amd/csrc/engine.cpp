@@ -2067,17 +2067,29 @@ struct mtsac_engine {
   // pcgrad -> clip_by_global_norm -> adam.  The per-task gradients come from the eval metrics' pass
   // (task_grads' halves); the surgery runs in Gram form (pcgrad.hip) and leaves mean_i g_i^pc in Net::g,
   // so optimize() -- clip, Adam, Polyak, planes -- runs unchanged.  Eager, on the main stream.
-  bool pc_on = false, pc_cos = false, pc_pinned = false, pc_graph_before = true;
+  //
+  // CAGrad (CAGradConfig: cagrad -> clip_by_global_norm -> adam; mtrl/optim/cagrad.py) is the same step
+  // with another solve between the Gram and the combine (cagrad.hip): `surgery` picks it.
+  enum { SURGERY_NONE = 0, SURGERY_PCGRAD = 1, SURGERY_CAGRAD = 2 };
+  static constexpr int CA_MAX_ITERS = 1024;  // obj_hist slots per network
+  int surgery = SURGERY_NONE;
+  bool pc_cos = false, pc_pinned = false, pc_graph_before = true;
   double *pc_gram = nullptr, *pc_c = nullptr;
   float *pc_w = nullptr, *pc_logs = nullptr, *pc_row_e = nullptr;  // [2][64], [2][8] (0 critic, 1 actor), [B]
   int *pc_perm = nullptr, *pc_pin = nullptr;                       // [2][64] orders used / pinned
+  int ca_iters = 21;
+  double ca_c = 0.5, ca_lr = 25.0, ca_momentum = 0.5;
+  bool ca_cos = false;
+  float* ca_tw = nullptr;                        // [2][64] task weights
+  double *ca_hist = nullptr, *ca_w0 = nullptr;   // [2][CA_MAX_ITERS] objectives, [64] a kernel-alone start
 
   int ensure_pcgrad_buffers() {
     int rc = 0;
     if (pc_gram) return 0;
     if ((rc = alloc(&pc_gram, 64 * 64)) || (rc = alloc(&pc_c, 64 * 64)) || (rc = alloc(&pc_w, 2 * 64)) ||
         (rc = alloc(&pc_logs, 2 * 8)) || (rc = alloc(&pc_row_e, (size_t)B)) || (rc = alloc(&pc_perm, 2 * 64)) ||
-        (rc = alloc(&pc_pin, 2 * 64)))
+        (rc = alloc(&pc_pin, 2 * 64)) || (rc = alloc(&ca_tw, 2 * 64)) ||
+        (rc = alloc(&ca_hist, 2 * (size_t)CA_MAX_ITERS)) || (rc = alloc(&ca_w0, 64)))
       return rc;
     return hipDeviceSynchronize() == hipSuccess ? 0 : fail(-5, "device synchronize");
   }
@@ -2113,10 +2125,31 @@ struct mtsac_engine {
     pcgrad_solve(s, cur);
   }
 
-  // Gram, solve, combine of network w (0 critic, 1 actor): Net::g = mean_i g_i^pc
+  // CAGrad's solve on pc_gram: combine weights into the pc_w slot, the four state scalars (+ the best
+  // iterate's index and |mean_t g_t|) into the pc_logs slot
+  void ca_solve_of(int w, double c, int iters, double lr, double momentum, const double* w0, bool cosine) {
+    CagradSolve s{};
+    s.gram = pc_gram;
+    s.T = T_l;
+    s.iters = iters;
+    s.c = c;
+    s.lr = lr;
+    s.momentum = momentum;
+    s.w0 = w0;
+    s.cosine_logs = cosine ? 1 : 0;
+    s.w = pc_w + 64 * w;
+    s.task_weights = ca_tw + 64 * w;
+    s.logs = pc_logs + 8 * w;
+    s.obj_hist = ca_hist + (size_t)CA_MAX_ITERS * w;
+    cagrad_solve(s, cur);
+  }
+
+  // Gram, solve, combine of network w (0 critic, 1 actor): Net::g = mean_i g_i^pc (PCGrad), or CAGrad's
+  // update
   void pc_surgery(Net& net, int w) {
     pc_gram_of(w);
-    pc_solve_of(w, pc_pinned ? pc_pin + 64 * w : nullptr, pc_cos);
+    if (surgery == SURGERY_CAGRAD) ca_solve_of(w, ca_c, ca_iters, ca_lr, ca_momentum, nullptr, ca_cos);
+    else pc_solve_of(w, pc_pinned ? pc_pin + 64 * w : nullptr, pc_cos);
     task_combine(tg[w], pc_w + 64 * w, T_l, tgP[w], pc_leaves(net), net.g, cur);
   }
 
@@ -3028,8 +3061,8 @@ int mtsac_update(mtsac_engine* h, const mtsac_batch* b, const float* eps_next, c
     HIP_TRY(hipMemcpyAsync(h->eps_c, eps_cur, sizeof(float) * B * A, hipMemcpyDefault, h->st));
   }
   h->tl_next = 0;
-  if (h->pc_on) {
-    if (h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
+  if (h->surgery) {
+    if (h->sharded()) return fail(-95, "PCGrad / CAGrad needs every task on one engine (unsharded)");
     h->pcgrad_step(b == nullptr, eps_next == nullptr);
   } else {
     h->step(b == nullptr, eps_next == nullptr);
@@ -3159,10 +3192,13 @@ int mtsac_set_pcgrad(mtsac_engine* h, int32_t on, int32_t cosine_sim_logs) {
   if (!h) return fail(-22, "null engine");
   if (!on) {
     HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->pc_on) h->use_graph = h->pc_graph_before;
-    h->pc_on = false;
+    if (h->surgery == mtsac_engine::SURGERY_PCGRAD) {
+      h->use_graph = h->pc_graph_before;
+      h->surgery = mtsac_engine::SURGERY_NONE;
+    }
     return 0;
   }
+  if (h->surgery == mtsac_engine::SURGERY_CAGRAD) return fail(-16, "CAGrad is on (mtsac_set_cagrad(0) first)");
   if (h->T_l != h->T_g || h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
   if (h->cfg.use_task_weights)
     return fail(-95, "PCGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
@@ -3177,9 +3213,9 @@ int mtsac_set_pcgrad(mtsac_engine* h, int32_t on, int32_t cosine_sim_logs) {
     h->gexec = nullptr;
     h->graph = nullptr;
   }
-  if (!h->pc_on) h->pc_graph_before = h->use_graph;
+  if (!h->surgery) h->pc_graph_before = h->use_graph;
   h->use_graph = false;
-  h->pc_on = true;
+  h->surgery = mtsac_engine::SURGERY_PCGRAD;
   h->pc_cos = cosine_sim_logs != 0;
   return 0;
 }
@@ -3283,12 +3319,100 @@ int mtsac_task_combine(mtsac_engine* h, int which, const float* w, float* out_de
   return 0;
 }
 
+// ---------------------------------------------------------------- CAGrad
+static int cagrad_args(double c, int32_t num_iterations, double learning_rate, double momentum) {
+  if (num_iterations < 1) return fail(-22, "CAGrad: num_iterations must be at least 1");
+  if (num_iterations > mtsac_engine::CA_MAX_ITERS) return fail(-22, "CAGrad: at most 1024 iterations");
+  if (!std::isfinite(c) || c < 0.0) return fail(-22, "CAGrad: c must be finite and not negative");
+  if (!std::isfinite(learning_rate) || !std::isfinite(momentum))
+    return fail(-22, "CAGrad: learning rate and momentum must be finite");
+  return 0;
+}
+
+int mtsac_set_cagrad(mtsac_engine* h, int32_t on, double c, int32_t num_iterations, double learning_rate,
+                     double momentum, int32_t cosine_sim_logs) {
+  if (!h) return fail(-22, "null engine");
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->surgery == mtsac_engine::SURGERY_CAGRAD) {
+      h->use_graph = h->pc_graph_before;
+      h->surgery = mtsac_engine::SURGERY_NONE;
+    }
+    return 0;
+  }
+  if (h->surgery == mtsac_engine::SURGERY_PCGRAD) return fail(-16, "PCGrad is on (mtsac_set_pcgrad(0) first)");
+  if (h->T_l != h->T_g || h->sharded()) return fail(-95, "CAGrad needs every task on one engine (unsharded)");
+  if (h->cfg.use_task_weights)
+    return fail(-95, "CAGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
+  if (h->T_l > 64) return fail(-22, "CAGrad: at most 64 tasks");
+  int rc = cagrad_args(c, num_iterations, learning_rate, momentum);
+  if (!rc) rc = h->ensure_task_grad_buffers();
+  if (!rc) rc = h->ensure_pcgrad_buffers();
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  if (h->gexec) {  // a captured plain step is not this mode's step
+    (void)hipGraphExecDestroy(h->gexec);
+    (void)hipGraphDestroy(h->graph);
+    h->gexec = nullptr;
+    h->graph = nullptr;
+  }
+  if (!h->surgery) h->pc_graph_before = h->use_graph;
+  h->use_graph = false;
+  h->surgery = mtsac_engine::SURGERY_CAGRAD;
+  h->ca_c = c;
+  h->ca_iters = num_iterations;
+  h->ca_lr = learning_rate;
+  h->ca_momentum = momentum;
+  h->ca_cos = cosine_sim_logs != 0;
+  return 0;
+}
+
+int mtsac_get_cagrad_logs(mtsac_engine* h, float* out) {
+  if (!h || !out) return fail(-22, "null argument");
+  if (!h->pc_gram) return fail(-22, "CAGrad is not set up (mtsac_set_cagrad)");
+  float l[16], tw[128];
+  HIP_TRY(hipMemcpyAsync(l, h->pc_logs, sizeof(l), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(tw, h->ca_tw, sizeof(tw), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  const int T = h->T_l;
+  for (int w = 0; w < 2; ++w) {
+    for (int k = 0; k < 4; ++k) out[(4 + T) * w + k] = l[8 * w + k];
+    for (int t = 0; t < T; ++t) out[(4 + T) * w + 4 + t] = tw[64 * w + t];
+  }
+  return h->check_err();
+}
+
+int mtsac_task_cagrad_solve(mtsac_engine* h, int which, double c, int32_t num_iterations, double learning_rate,
+                            double momentum, const double* w0, int32_t cosine_sim_logs, float* w,
+                            float* task_weights, float* logs, double* obj_hist) {
+  int rc = task_grad_ready(h, which);
+  if (rc) return rc;
+  if (!w || !task_weights || !logs || !obj_hist) return fail(-22, "null argument");
+  if (h->T_l > 64) return fail(-22, "CAGrad: at most 64 tasks");
+  if ((rc = cagrad_args(c, num_iterations, learning_rate, momentum))) return rc;
+  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  const int T = h->T_l;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  if (w0) HIP_TRY(hipMemcpy(h->ca_w0, w0, sizeof(double) * T, hipMemcpyHostToDevice));
+  h->cur = h->st;
+  h->pc_gram_of(which);
+  h->ca_solve_of(which, c, num_iterations, learning_rate, momentum, w0 ? h->ca_w0 : nullptr, cosine_sim_logs != 0);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(w, h->pc_w + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(task_weights, h->ca_tw + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(logs, h->pc_logs + 8 * which, sizeof(float) * 6, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(obj_hist, h->ca_hist + (size_t)mtsac_engine::CA_MAX_ITERS * which,
+                         sizeof(double) * num_iterations, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  return 0;
+}
+
 int mtsac_update_many(mtsac_engine* h, int32_t steps) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
   if (steps <= 0) return 0;
-  if (h->pc_on) {  // eager, one stream, no overlap between steps; the task orders are drawn on the device
-    if (h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
+  if (h->surgery) {  // eager, one stream, no overlap between steps; PCGrad's task orders are drawn on the device
+    if (h->sharded()) return fail(-95, "PCGrad / CAGrad needs every task on one engine (unsharded)");
     h->tl_next = 0;
     for (int s = 0; s < steps; ++s) h->pcgrad_step(true, true);
     HIP_TRY(hipGetLastError());
@@ -3336,7 +3460,8 @@ int mtsac_get_logs(mtsac_engine* h, float* logs) {
 
 int mtsac_enable_graph(mtsac_engine* h, int32_t enable) {
   if (!h) return fail(-22, "null engine");
-  if (enable && h->pc_on) return fail(-95, "the PCGrad step is not captured: graph replay is unavailable in this mode");
+  if (enable && h->surgery)
+    return fail(-95, "the PCGrad / CAGrad step is not captured: graph replay is unavailable in this mode");
   h->use_graph = enable != 0;
   return 0;
 }

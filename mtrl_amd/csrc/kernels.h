@@ -652,6 +652,27 @@ void task_combine(const float* M, const float* w, int T, long long P, const Pcgr
 void pcgrad_logs(const float* solve_critic, const float* solve_actor, const float* row_explore, int B, float* logs,
                  hipStream_t st);
 
+// ------------------------------------------------------------------ CAGrad in Gram form (cagrad.hip;
+// mtrl/optim/cagrad.py).  One wavefront, fp64, on the Gram matrix task_gram left: the per-task clip to
+// norm 1 folded into the matrix, the scaling, the momentum-SGD weight search (iters - 1 steps and a final
+// evaluation, best iterate kept), the softmax and the combine weights on the RAW rows, so task_combine
+// runs on M as it is.
+struct CagradSolve {
+  const double* gram;   // [T*T]
+  int T;
+  int iters;            // num_iterations (>= 1): evaluations of the objective
+  double c, lr, momentum;
+  const double* w0;     // device [T] start of the search, or null: zeros (the reference's)
+  int cosine_logs;
+  float* w;             // [T] combine weights s_t (1/T + tw_t lambda) / (1 + c^2)
+  float* task_weights;  // [T] softmax(w_best)
+  float* logs;          // [6]: avg_grad_magnitude, avg_grad_magnitude_before_surgery, avg_cosine_similarity
+                        // (NaN without cosine_logs), cagrad_objective, the best iterate's index,
+                        // |mean_t g_t| (the pre-surgery norm, where pcgrad_logs reads it)
+  double* obj_hist;     // [iters] the objective at every evaluated iterate
+};
+void cagrad_solve(const CagradSolve& s, hipStream_t st);
+
 // sets what mtsac_last_error returns on this thread (engine.cpp; the debug entry points name a
 // written guard band through it)
 void set_last_error(const char* msg);

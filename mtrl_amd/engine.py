@@ -18,6 +18,10 @@ from ._lib import LOG_KEYS, Batch, Config, MTSACError, check
 # PCGradState fields (mtrl/optim/pcgrad.py:12-17), the order of mtsac_get_pcgrad_logs per network
 PCGRAD_LOG_KEYS = ("n_grad_conflicts", "avg_grad_magnitude", "avg_grad_magnitude_before_surgery",
                    "avg_cosine_similarity", "avg_cosine_similarity_diff")
+# CAGradState fields (mtrl/optim/cagrad.py:12-17); mtsac_get_cagrad_logs holds the four scalars, then
+# task_weights
+CAGRAD_LOG_KEYS = ("task_weights", "avg_grad_magnitude", "avg_grad_magnitude_before_surgery",
+                   "avg_cosine_similarity", "cagrad_objective")
 
 
 def _ptr(x) -> tuple[int, Any]:
@@ -291,6 +295,49 @@ class MTSACEngine:
         out = np.empty(self.task_gradient_size(which), np.float32)
         check(self.lib.mtsac_task_combine(self._h, which, w.ctypes.data, out.ctypes.data))
         return out
+
+    # ------------------------------------------------------------------ CAGrad (include/mtsac.h)
+    def set_cagrad(self, on: bool, c: float = 0.5, num_iterations: int = 21, learning_rate: float | None = None,
+                   momentum: float = 0.5, cosine_sim_logs: bool = False) -> None:
+        """CAGrad on both optimizers: update / update_many run the CAGrad step.  The defaults are the
+        reference's (learning_rate None: 25 below 50 tasks, 50 from there on)."""
+        lr = (25.0 if self.T_l < 50 else 50.0) if learning_rate is None else float(learning_rate)
+        check(self.lib.mtsac_set_cagrad(self._h, 1 if on else 0, float(c), int(num_iterations), lr, float(momentum),
+                                        1 if cosine_sim_logs else 0))
+
+    def cagrad_logs(self) -> dict:
+        """``metrics/{critic,actor}_<CAGradState field>``; task_weights a float32 array of length T."""
+        T = self.T_l
+        out = np.empty(2 * (4 + T), np.float32)
+        check(self.lib.mtsac_get_cagrad_logs(self._h, out.ctypes.data))
+        logs = {}
+        for w, net in enumerate(("critic", "actor")):
+            o = (4 + T) * w
+            logs[f"metrics/{net}_task_weights"] = out[o + 4:o + 4 + T].copy()
+            for i, k in enumerate(CAGRAD_LOG_KEYS[1:]):
+                logs[f"metrics/{net}_{k}"] = float(out[o + i])
+        return logs
+
+    def task_cagrad_solve(self, which: int, c: float = 0.5, num_iterations: int = 21,
+                          learning_rate: float | None = None, momentum: float = 0.5, w0=None,
+                          cosine_sim_logs: bool = False):
+        """(w [T] float32 combine weights on the raw rows, logs) of the device solve on the matrix
+        set_task_gradients / task_gradients left: logs holds the CAGradState fields, ``grad_magnitude``,
+        ``best_iteration`` and ``obj_hist`` [num_iterations] (float64).  ``w0``: the search's start
+        (None: zeros, the reference's)."""
+        T = self.T_l
+        lr = (25.0 if T < 50 else 50.0) if learning_rate is None else float(learning_rate)
+        w0a = None if w0 is None else np.ascontiguousarray(w0, np.float64).reshape(T)
+        n = max(int(num_iterations), 1)
+        w, tw, lg, hist = np.empty(T, np.float32), np.empty(T, np.float32), np.empty(6, np.float32), np.empty(n)
+        check(self.lib.mtsac_task_cagrad_solve(self._h, which, float(c), int(num_iterations), lr, float(momentum),
+                                               None if w0a is None else w0a.ctypes.data,
+                                               1 if cosine_sim_logs else 0, w.ctypes.data, tw.ctypes.data,
+                                               lg.ctypes.data, hist.ctypes.data))
+        logs = {"task_weights": tw}
+        logs.update({k: float(v) for k, v in zip(CAGRAD_LOG_KEYS[1:], lg[:4])})
+        logs.update(best_iteration=int(lg[4]), grad_magnitude=float(lg[5]), obj_hist=hist)
+        return w, logs
 
     def update_many(self, steps: int) -> None:
         check(self.lib.mtsac_update_many(self._h, steps))

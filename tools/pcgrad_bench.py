@@ -15,6 +15,9 @@ Kernel times: run the PCGrad steps alone under the profiler, in a run of its own
 then ``--stats-csv OUT/.../*_kernel_stats.csv --configs mt50_w2048`` turns the per-kernel averages of
 gram_kernel / combine_kernel (one launch per network per step) into achieved bytes/s over
 (T P + P) 4 bytes per launch, against the 6.29 TB/s float4-copy rate (MI355X_MICROARCH.md).
+``--surgery cagrad`` adds the CAGrad step on a third engine of the same tree: the
+three steps alternate within every repeat, ``--profile-steps`` runs CAGrad steps, and the kernel table
+lists cagrad_solve_kernel beside pcgrad_solve_kernel.
 Needs the GPU (except --stats-csv): there is no fallback.
 """
 
@@ -44,7 +47,8 @@ def param_counts(T, W, depth=3, A=4, E=2):
     return net(39 + T + A, 1, E), net(39 + T, 2 * A, 1)
 
 
-def make_engine(T, W, n, precision, pcgrad):
+def make_engine(T, W, n, precision, surgery):
+    """surgery: None (the plain eager step), "pcgrad" or "cagrad"."""
     from mtrl_amd import _lib as L
     from mtrl_amd.engine import MTSACEngine, make_config
     from mtrl_amd.init import init_mtsac
@@ -58,8 +62,8 @@ def make_engine(T, W, n, precision, pcgrad):
     e.buffer_fill_synthetic(7)
     e.seed_rng(1)
     e.enable_graph(False)
-    if pcgrad:
-        e.set_pcgrad(True)
+    if surgery:
+        e.set_pcgrad(True) if surgery == "pcgrad" else e.set_cagrad(True)
         assert (e.task_gradient_size(0), e.task_gradient_size(1)) == param_counts(T, W)
     return e
 
@@ -85,7 +89,8 @@ def kernel_rates(stats_csv, T, W):
     out = {}
     with open(stats_csv, newline="") as f:
         for row in csv.DictReader(f):
-            for key in ("gram_kernel", "combine_kernel", "gram_sum_kernel", "pcgrad_solve_kernel"):
+            for key in ("gram_kernel", "combine_kernel", "gram_sum_kernel", "pcgrad_solve_kernel",
+                        "cagrad_solve_kernel"):
                 if f"::{key}" in row["Name"] or row["Name"].startswith(key):
                     avg = float(row["AverageNs"]) * 1e-9
                     out[key] = {"calls": int(row["Calls"]), "avg_us": 1e6 * avg}
@@ -101,7 +106,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--profile-steps", type=int, default=0, help="only run this many PCGrad steps (for rocprofv3)")
+    ap.add_argument("--surgery", default="pcgrad", choices=["pcgrad", "cagrad"],
+                    help="cagrad: time the CAGrad step too, alternating with the other two")
+    ap.add_argument("--profile-steps", type=int, default=0,
+                    help="only run this many steps of --surgery's kind (for rocprofv3)")
     ap.add_argument("--stats-csv", default=None, help="rocprofv3 kernel-stats CSV of a --profile-steps run")
     args = ap.parse_args()
 
@@ -110,27 +118,39 @@ def main():
         if args.stats_csv:
             print(json.dumps({"config": name, "kernels": kernel_rates(args.stats_csv, T, W)}), flush=True)
             continue
-        pc = make_engine(T, W, n, args.precision, True)
         if args.profile_steps:
-            pc.update_many(args.profile_steps)
-            pc.synchronize()
-            pc.close()
+            e = make_engine(T, W, n, args.precision, args.surgery)
+            e.update_many(args.profile_steps)
+            e.synchronize()
+            e.close()
             continue
-        plain = make_engine(T, W, n, args.precision, False)
+        pc = make_engine(T, W, n, args.precision, "pcgrad")
+        plain = make_engine(T, W, n, args.precision, None)
+        ca = make_engine(T, W, n, args.precision, "cagrad") if args.surgery == "cagrad" else None
         plain.update_many(args.warmup)
         pc.update_many(args.warmup)
-        tp, tq = [], []
+        if ca:
+            ca.update_many(args.warmup)
+        tp, tq, tc = [], [], []
         for _ in range(args.repeats):
             tp.append(time_steps(plain, args.steps))
             tq.append(time_steps(pc, args.steps))
+            if ca:
+                tc.append(time_steps(ca, args.steps))
         logs = pc.logs() | pc.pcgrad_logs()
-        print(json.dumps({
+        if ca:
+            logs |= {k: v for k, v in ca.cagrad_logs().items() if np.ndim(v) == 0}
+        out = {
             "config": name, "T": T, "width": W, "batch": n * T, "precision": args.precision, "steps": args.steps,
             "plain_eager_step": spread(tp), "pcgrad_step": spread(tq),
             "ratio_pcgrad_over_plain": statistics.median(tq) / statistics.median(tp),
             "critic_P": pc.task_gradient_size(0), "actor_P": pc.task_gradient_size(1),
             "finite_logs": bool(all(np.isfinite(v) for k, v in logs.items() if "cosine" not in k)),
-        }), flush=True)
+        }
+        if ca:
+            out |= {"cagrad_step": spread(tc), "ratio_cagrad_over_pcgrad": statistics.median(tc) / statistics.median(tq)}
+            ca.close()
+        print(json.dumps(out), flush=True)
         plain.close()
         pc.close()
 
