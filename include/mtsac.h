@@ -343,6 +343,46 @@ int mtsac_task_cagrad_solve(mtsac_engine* h, int which, double c, int32_t num_it
                             double momentum, const double* w0, int32_t cosine_sim_logs, float* w,
                             float* task_weights, float* logs /* 6 */, double* obj_hist);
 
+/* ---- GradNorm (GradNormConfig on both optimizers, mtrl/config/optim.py and mtrl/optim/gradnorm.py).
+ * DESIGN.md section 12.  The same split-loss step with a third solve between the Gram matrix and the
+ * combine.  It also consumes the per-task loss values and carries state from step to step: T task weights
+ * (normalised to sum T), the latched first losses (+inf until then), and an inner [clip_by_global_norm +]
+ * Adam on the weights.  Read literally, the reference's loss does not depend on the weights, so their
+ * gradient is exactly zero: the weights stay the normalised initial_weights and the update is
+ * sum_t w_t s_t g_t (a sum over the tasks, s_t the per-task clip to norm 1.0).  weighted_norms = 1 is the
+ * form the reference has commented out (the task norms multiplied by the weights), where the weights move.
+ * Arrays of two are indexed 0 critic, 1 actor.
+ * mtsac_set_gradnorm: on = 1 makes mtsac_update / mtsac_update_many run the GradNorm step for BOTH networks
+ * and (re-)initialises the state from initial_weights ([2][T], NULL: ones).  per_task_clip is
+ * bool(GradNormConfig.max_grad_norm); inner_* are the gradnorm_optimizer's lr, eps and max_grad_norm
+ * (negative: no clip).  Limits and error codes as mtsac_set_cagrad (-95 sharded or use_task_weights, -22
+ * above 64 tasks, -12 out of memory, eager step: mtsac_enable_graph(1) returns -95 while on); -16 while
+ * PCGrad or CAGrad is on (and their setters return -16 while GradNorm is on); -22 for non-finite values or
+ * initial_weights that sum to zero.  Log slots 2, 5, 7 as in the PCGrad step.
+ * mtsac_gradnorm_get_state / _set_state: one network's state (for a checkpoint, or an engine rebuilt at
+ * another geometry); count is the inner Adam's.
+ * mtsac_get_gradnorm_logs: per network (critic, then actor) the T task_weights, the T original_losses,
+ * gradnorm_loss of the last step: out[2 * (2 T + 1)].
+ * mtsac_get_gradnorm_task_losses: the per-task loss values the last step's solves read: out[2][T].
+ * mtsac_task_gradnorm_solve: the kernel alone, on the matrix mtsac_set_task_gradients /
+ * mtsac_task_gradients left, with the task losses and the state passed in: the state arrays and count are
+ * read and overwritten with the new state; w[T] are the combine weights on the raw rows (for
+ * mtsac_task_combine); logs[3] = gradnorm_loss, the sign margin min_t |d_t| / mean(n), |mean_t g_t|. */
+int mtsac_set_gradnorm(mtsac_engine* h, int32_t on, double asymmetry, const int32_t* per_task_clip /* 2 */,
+                       const double* inner_lr /* 2 */, const double* inner_eps /* 2 */,
+                       const double* inner_max_grad_norm /* 2 */, const float* initial_weights /* [2][T] or NULL */,
+                       int32_t weighted_norms);
+int mtsac_gradnorm_get_state(mtsac_engine* h, int which, float* task_weights, float* original_losses, float* mu,
+                             float* nu, int64_t* count);
+int mtsac_gradnorm_set_state(mtsac_engine* h, int which, const float* task_weights, const float* original_losses,
+                             const float* mu, const float* nu, int64_t count);
+int mtsac_get_gradnorm_logs(mtsac_engine* h, float* out /* 2 * (2 T + 1) */);
+int mtsac_get_gradnorm_task_losses(mtsac_engine* h, float* out /* 2 * T */);
+int mtsac_task_gradnorm_solve(mtsac_engine* h, int which, const float* task_losses, double asymmetry,
+                              int32_t per_task_clip, double inner_lr, double inner_eps, double inner_max_grad_norm,
+                              int32_t weighted_norms, float* task_weights, float* original_losses, float* mu,
+                              float* nu, int64_t* count, float* w, float* logs /* 3 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -158,6 +158,13 @@ SIGNATURES = {
     "mtsac_get_cagrad_logs": (ctypes.c_int, [P, P]),
     "mtsac_task_cagrad_solve": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_double, I32, ctypes.c_double,
                                                ctypes.c_double, P, I32, P, P, P, P]),
+    "mtsac_set_gradnorm": (ctypes.c_int, [P, I32, ctypes.c_double, P, P, P, P, P, I32]),
+    "mtsac_gradnorm_get_state": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, P]),
+    "mtsac_gradnorm_set_state": (ctypes.c_int, [P, ctypes.c_int, P, P, P, P, ctypes.c_int64]),
+    "mtsac_get_gradnorm_logs": (ctypes.c_int, [P, P]),
+    "mtsac_get_gradnorm_task_losses": (ctypes.c_int, [P, P]),
+    "mtsac_task_gradnorm_solve": (ctypes.c_int, [P, ctypes.c_int, P, ctypes.c_double, I32, ctypes.c_double,
+                                                 ctypes.c_double, ctypes.c_double, I32, P, P, P, P, P, P, P]),
     "mtsac_debug_gemm_bench": (ctypes.c_int, [ctypes.c_int] * 8 + [PD]),
     "mtsac_debug_gemm_x3p": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
     "mtsac_debug_gemm_x3p_bench": (ctypes.c_int, [ctypes.c_int] * 6 + [PD]),

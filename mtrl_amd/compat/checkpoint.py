@@ -18,6 +18,13 @@ mtrl/nn/multi_head.py:20-68, mtrl/rl/networks.py:21-67,208-222):
     alpha/params/params/log_alpha, alpha/opt_state/0/{mu,nu}/params/log_alpha, .../0/count
     {actor,critic,alpha}/step, key
 
+With GradNormConfig on both networks the optimizer is optax.chain(gradnorm(...), OptimizerConfig.spawn())
+and the opt_state one level deeper, as the reference's chain lays it out:
+
+    {actor,critic}/opt_state/0/{task_weights,original_losses}              (GradNormState)
+    {actor,critic}/opt_state/0/opt_state/<opt_prefix(inner clip)>/{count,mu,nu}   (the inner Adam on the weights)
+    {actor,critic}/opt_state/1/<opt_prefix(outer clip)>/{count,mu,nu}      (the outer clipped Adam)
+
 (TrainState.params is the whole flax variables dict, hence ``params/params``; the optax
 state nesting follows ``OptimizerConfig.spawn``: see ``opt_prefix``.)
 
@@ -121,10 +128,17 @@ def _unflatten_paths(flat: dict, prefix: str) -> dict:
     return tree
 
 
-def agent_tree(kw: dict, get, count, key=None) -> dict[str, np.ndarray]:
+def _gradnorm_prefix(gradnorm) -> tuple[str, ...]:
+    return ("1",) if gradnorm is not None else ()
+
+
+def agent_tree(kw: dict, get, count, key=None, gradnorm=None) -> dict[str, np.ndarray]:
     """The MTSAC pytree (mtsac.py:130-151: actor / critic / alpha TrainStates + key) as
     {flax path: array}.  ``get(which)`` returns an engine flat vector (include/mtsac.h ids),
-    ``count(i)`` the Adam count of actor (0) / critic (1) / alpha (2)."""
+    ``count(i)`` the Adam count of actor (0) / critic (1) / alpha (2).  ``gradnorm``: None, or
+    (get_state, inner_clips) with GradNormConfig on both networks -- ``get_state(w)`` the
+    ``mtrl_amd.gradnorm.GradNormState`` of the critic (0) / actor (1), ``inner_clips`` their
+    gradnorm_optimizer.max_grad_norm in that order."""
     ash, csh = network_shapes(kw, "actor"), network_shapes(kw, "critic")
 
     def state(which_p, which_mu, which_nu, shapes, root, i, clip, extra=None):
@@ -133,7 +147,19 @@ def agent_tree(kw: dict, get, count, key=None) -> dict[str, np.ndarray]:
                 "nu": to_flax_tree(get(which_nu), shapes, root)}
         opt: dict = {}
         node = opt
-        pre = opt_prefix(clip)
+        pre = _gradnorm_prefix(gradnorm) + opt_prefix(clip)
+        if gradnorm is not None:
+            w = 1 - i  # networks here: actor 0, critic 1; GradNorm states: critic 0, actor 1
+            st = gradnorm[0](w)
+            inner: dict = {}
+            nd = inner
+            ipre = opt_prefix(gradnorm[1][w])
+            for k in ipre[:-1]:
+                nd = nd.setdefault(k, {})
+            nd[ipre[-1]] = {"count": np.int32(st.count), "mu": np.asarray(st.mu, np.float32),
+                            "nu": np.asarray(st.nu, np.float32)}
+            opt["0"] = {"task_weights": np.asarray(st.task_weights, np.float32),
+                        "original_losses": np.asarray(st.original_losses, np.float32), "opt_state": inner}
         for k in pre[:-1]:
             node = node.setdefault(k, {})
         node[pre[-1]] = adam
@@ -171,11 +197,18 @@ def agent_state(algo) -> dict[str, np.ndarray]:
     engine's action-noise stream position in place of the JAX PRNG key (threefry is not
     reproduced): [noise seed, draws so far]."""
     eng = algo.engine
-    return agent_tree(algo._cfg_kwargs, eng.get_params, eng.get_adam_count, key=algo.noise_key())
+    return agent_tree(algo._cfg_kwargs, eng.get_params, eng.get_adam_count, key=algo.noise_key(),
+                      gradnorm=(eng.gradnorm_state, _inner_clips(algo)) if getattr(algo, "gradnorm", False) else None)
 
 
-def load_agent_tree(kw: dict, flat: dict, put, set_count) -> None:
-    """Inverse of ``agent_tree``: ``put(which, flat_vector)``, ``set_count(i, n)``."""
+def _inner_clips(algo) -> tuple:
+    return tuple(c.network_config.optimizer.gradnorm_optimizer.max_grad_norm
+                 for c in (algo.config.critic_config, algo.config.actor_config))
+
+
+def load_agent_tree(kw: dict, flat: dict, put, set_count, gradnorm=None) -> None:
+    """Inverse of ``agent_tree``: ``put(which, flat_vector)``, ``set_count(i, n)``; ``gradnorm``: None or
+    (put_state, inner_clips), ``put_state(w, GradNormState)``."""
     ash, csh = network_shapes(kw, "actor"), network_shapes(kw, "critic")
     a = _unflatten_paths(flat, "actor")
     c = _unflatten_paths(flat, "critic")
@@ -183,9 +216,10 @@ def load_agent_tree(kw: dict, flat: dict, put, set_count) -> None:
 
     def adam(ts, clip, what):
         node = ts["opt_state"]
-        for k in opt_prefix(clip):
+        pre = (_gradnorm_prefix(gradnorm) if what != "alpha" else ()) + opt_prefix(clip)
+        for k in pre:
             if k not in node:
-                raise KeyError(f"{what}/opt_state/{'/'.join(opt_prefix(clip))}: missing (max_grad_norm={clip})")
+                raise KeyError(f"{what}/opt_state/{'/'.join(pre)}: missing (max_grad_norm={clip})")
             node = node[k]
         return node
 
@@ -204,11 +238,27 @@ def load_agent_tree(kw: dict, flat: dict, put, set_count) -> None:
     put(L.ALPHA_ADAM_NU, np.asarray(la["nu"]["params"]["log_alpha"], np.float32))
     for i, st in enumerate((aa, ca, la)):
         set_count(i, int(st["count"]))
+    if gradnorm is not None:
+        from ..gradnorm import GradNormState
+
+        for w, (ts, what) in enumerate(((c, "critic"), (a, "actor"))):
+            gs = ts["opt_state"].get("0", {})
+            node = gs.get("opt_state", {})
+            ipre = opt_prefix(gradnorm[1][w])
+            for k in ipre:
+                if k not in node:
+                    raise KeyError(f"{what}/opt_state/0/opt_state/{'/'.join(ipre)}: missing (GradNorm's inner Adam)")
+                node = node[k]
+            gradnorm[0](w, GradNormState(
+                task_weights=np.asarray(gs["task_weights"], np.float32),
+                original_losses=np.asarray(gs["original_losses"], np.float32), count=int(node["count"]),
+                mu=np.asarray(node["mu"], np.float32), nu=np.asarray(node["nu"], np.float32)))
 
 
 def load_agent_state(algo, flat: dict) -> None:
     """Inverse of ``agent_state``: push every leaf back into the engine."""
     eng = algo.engine
-    load_agent_tree(algo._cfg_kwargs, flat, eng.set_params, eng.set_adam_count)
+    load_agent_tree(algo._cfg_kwargs, flat, eng.set_params, eng.set_adam_count,
+                    gradnorm=(eng.set_gradnorm_state, _inner_clips(algo)) if getattr(algo, "gradnorm", False) else None)
     if "key" in flat:
         algo.set_noise_key(np.asarray(flat["key"]))

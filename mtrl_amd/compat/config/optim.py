@@ -54,3 +54,23 @@ class CAGradConfig(OptimizerConfig):
     @property
     def requires_split_task_losses(self) -> bool:
         return True
+
+
+@dataclass(frozen=True, kw_only=True)
+class GradNormConfig(OptimizerConfig):
+    """config/optim.py:75-98: optax.chain(gradnorm(num_tasks, gradnorm_optimizer, asymmetry,
+    initial_weights, max_grad_norm), clip, adam).  ``gradnorm_optimizer`` is the inner optimizer of the T
+    task weights; a truthy ``max_grad_norm`` also clips every task gradient to norm 1.0 (not to
+    max_grad_norm: clip_per_task_grads is called with its default bound).  The engine runs the weight step
+    in Gram form on the per-task gradients and losses (mtrl_amd/csrc/gradnorm.hip); both the actor's and
+    the critic's optimizer must be GradNorm."""
+
+    num_tasks: int
+    gradnorm_optimizer: OptimizerConfig
+    initial_weights: Any | None = None
+    asymmetry: float = 0.12
+    max_grad_norm: float | None = None
+
+    @property
+    def requires_split_task_losses(self) -> bool:
+        return True

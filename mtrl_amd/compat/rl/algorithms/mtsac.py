@@ -7,7 +7,8 @@ lives in one ``MTSACEngine`` (device memory, mutated in place; methods return ``
 Supported: multi-head MLP actor/critic (MultiHeadConfig or VanillaNetworkConfig with
 num_tasks from the algorithm config), MSE critic, Adam optimizers -- the north-star path --
 PCGrad gradient surgery on both networks (PCGradConfig, experiments/misc/mt10_mtmhsac_pcgrad.py) and
-CAGrad on both networks (CAGradConfig, experiments/misc/mt10_mtmhsac_cagrad.py).
+CAGrad or GradNorm on both networks (CAGradConfig, experiments/misc/mt10_mtmhsac_cagrad.py; GradNormConfig,
+experiments/misc/mt10_mtmhsac_gradnorm.py).
 """
 
 from __future__ import annotations
@@ -18,10 +19,10 @@ from collections.abc import Mapping
 import numpy as np
 
 from .... import _lib as L
-from ....engine import CAGRAD_LOG_KEYS, PCGRAD_LOG_KEYS, MTSACEngine, make_config
+from ....engine import CAGRAD_LOG_KEYS, GRADNORM_LOG_KEYS, PCGRAD_LOG_KEYS, MTSACEngine, make_config
 from ....init import init_mtsac
 from ...config.networks import ContinuousActionPolicyConfig, QValueFunctionConfig
-from ...config.optim import CAGradConfig, OptimizerConfig, PCGradConfig
+from ...config.optim import CAGradConfig, GradNormConfig, OptimizerConfig, PCGradConfig
 from ...config.rl import AlgorithmConfig
 from ...config.utils import Activation, Initializer, Optimizer
 from ..buffers import MultiTaskReplayBuffer
@@ -45,8 +46,8 @@ class MTSACConfig(AlgorithmConfig):
 class _DeviceLogs(Mapping):
     """The update's LogDict, fetched from the device on first access (like jax.device_get)."""
 
-    def __init__(self, engine: MTSACEngine, pcgrad: bool = False, cagrad: bool = False):
-        self._engine, self._d, self._pcgrad, self._cagrad = engine, None, pcgrad, cagrad
+    def __init__(self, engine: MTSACEngine, pcgrad: bool = False, cagrad: bool = False, gradnorm: bool = False):
+        self._engine, self._d, self._pcgrad, self._cagrad, self._gradnorm = engine, None, pcgrad, cagrad, gradnorm
 
     def _get(self):
         if self._d is None:
@@ -55,6 +56,10 @@ class _DeviceLogs(Mapping):
                 self._d.update(self._engine.pcgrad_logs())
             if self._cagrad:  # the CAGradState of both optimizers (mtrl/optim/cagrad.py:12-17)
                 self._d.update(self._engine.cagrad_logs())
+            if self._gradnorm:  # the GradNormState arrays of both optimizers (mtrl/optim/gradnorm.py:34-37)
+                g = self._engine.gradnorm_logs()
+                self._d.update({f"metrics/{net}_{k}": g[f"metrics/{net}_{k}"] for net in ("critic", "actor")
+                                for k in GRADNORM_LOG_KEYS})
         return self._d
 
     def __getitem__(self, k):
@@ -65,7 +70,8 @@ class _DeviceLogs(Mapping):
 
     def __len__(self):
         return (len(L.LOG_KEYS) + (2 * len(PCGRAD_LOG_KEYS) if self._pcgrad else 0) +
-                (2 * len(CAGRAD_LOG_KEYS) if self._cagrad else 0))
+                (2 * len(CAGRAD_LOG_KEYS) if self._cagrad else 0) +
+                (2 * len(GRADNORM_LOG_KEYS) if self._gradnorm else 0))
 
 
 def _check_supported(net, what: str):
@@ -75,10 +81,11 @@ def _check_supported(net, what: str):
         raise NotImplementedError(f"{what}: only he_uniform trunk init is implemented")
     if not getattr(net, "use_bias", True):
         raise NotImplementedError(f"{what}: use_bias=False is not implemented")
-    split = net.optimizer.requires_split_task_losses and not isinstance(net.optimizer, (PCGradConfig, CAGradConfig))
+    split = net.optimizer.requires_split_task_losses and not isinstance(
+        net.optimizer, (PCGradConfig, CAGradConfig, GradNormConfig))
     if net.optimizer.optimizer is not Optimizer.Adam or split:
         raise NotImplementedError(
-            f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad or CAGrad")
+            f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad, CAGrad or GradNorm")
 
 
 def _check_pcgrad(config: "MTSACConfig", task_shard) -> bool:
@@ -133,6 +140,57 @@ def _check_cagrad(config: "MTSACConfig", task_shard) -> bool:
     return True
 
 
+def _check_gradnorm(config: "MTSACConfig", task_shard) -> bool:
+    """True when both optimizers are GradNorm; raises for what the engine's GradNorm step does not run."""
+    opt_a = config.actor_config.network_config.optimizer
+    opt_c = config.critic_config.network_config.optimizer
+    ga, gc = isinstance(opt_a, GradNormConfig), isinstance(opt_c, GradNormConfig)
+    if not (ga or gc):
+        return False
+    if ga != gc:
+        raise NotImplementedError(
+            "GradNorm on one network only: the reference hands the critic's optimizer per-task gradients only "
+            "when the ACTOR's optimizer asks for split losses (mtsac.py:581), and gradnorm's shape assert fails "
+            "on anything else; give both actor and critic a GradNormConfig")
+    if opt_a.num_tasks != config.num_tasks or opt_c.num_tasks != config.num_tasks:
+        raise ValueError("GradNormConfig.num_tasks must equal the algorithm's num_tasks")
+    if config.use_task_weights:
+        raise NotImplementedError(
+            "GradNorm with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
+            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
+    if task_shard is not None:
+        raise NotImplementedError(
+            "GradNorm on a task-sharded engine: the task weights are renormalised over every task, so all "
+            "tasks' gradients and losses must be on one engine")
+    for what, opt in (("actor", opt_a), ("critic", opt_c)):
+        inner = opt.gradnorm_optimizer
+        if inner.optimizer is not Optimizer.Adam or inner.requires_split_task_losses:
+            raise NotImplementedError(f"{what}: GradNormConfig.gradnorm_optimizer must be a plain Adam OptimizerConfig")
+        if inner.max_grad_norm is not None and float(inner.max_grad_norm) == 0.0:
+            raise ValueError(
+                f"{what}: gradnorm_optimizer.max_grad_norm = 0.0: optax.clip_by_global_norm divides the zero "
+                "gradient of the task weights by its zero norm (NaN weights in the reference)")
+    if opt_a.asymmetry != opt_c.asymmetry:
+        raise NotImplementedError("GradNorm: actor and critic asymmetry differ; the engine holds one value")
+    return True
+
+
+def _gradnorm_args(config: "MTSACConfig") -> dict:
+    """MTSACEngine.set_gradnorm's arguments from the two GradNormConfigs, (critic, actor) pairs."""
+    oc = config.critic_config.network_config.optimizer
+    oa = config.actor_config.network_config.optimizer
+    iw = None
+    if oc.initial_weights is not None or oa.initial_weights is not None:
+        T = config.num_tasks
+        iw = np.stack([np.ones(T, np.float32) if o.initial_weights is None
+                       else np.asarray(o.initial_weights, np.float32).reshape(T) for o in (oc, oa)])
+    return dict(asymmetry=oa.asymmetry, per_task_clip=(bool(oc.max_grad_norm), bool(oa.max_grad_norm)),
+                inner_lr=(oc.gradnorm_optimizer.lr, oa.gradnorm_optimizer.lr),
+                inner_eps=(oc.gradnorm_optimizer.adam_eps, oa.gradnorm_optimizer.adam_eps),
+                inner_max_grad_norm=(oc.gradnorm_optimizer.max_grad_norm, oa.gradnorm_optimizer.max_grad_norm),
+                initial_weights=iw)
+
+
 class MTSAC(OffPolicyAlgorithm):
     def __init__(self, config: MTSACConfig, env_config, seed: int, engine: MTSACEngine, cfg_kwargs: dict):
         self.config = config
@@ -146,6 +204,7 @@ class MTSAC(OffPolicyAlgorithm):
         self.target_entropy = -float(np.prod(env_config.action_space.shape))
         self.pcgrad = False  # both optimizers PCGrad: the engine runs the gradient-surgery step
         self.cagrad = False  # both optimizers CAGrad: the same step with CAGrad's solve
+        self.gradnorm = False  # both optimizers GradNorm: the same step with GradNorm's stateful solve
 
     # ------------------------------------------------------------------ construction
     @staticmethod
@@ -160,6 +219,7 @@ class MTSAC(OffPolicyAlgorithm):
         _check_supported(net_c, "critic")
         pcgrad = _check_pcgrad(config, task_shard)
         cagrad = _check_cagrad(config, task_shard)
+        gradnorm = _check_gradnorm(config, task_shard)
         if task_shard is not None:
             raise NotImplementedError("task sharding is driven through mtrl_amd.shard, not this trainer")
         T = config.num_tasks
@@ -182,6 +242,8 @@ class MTSAC(OffPolicyAlgorithm):
             eng.set_pcgrad(True, net_a.optimizer.cosine_sim_logs)
         if cagrad:
             eng.set_cagrad(True)  # cagrad()'s defaults, as CAGradConfig.spawn calls it
+        if gradnorm:
+            eng.set_gradnorm(True, **_gradnorm_args(config))
         a, q = init_mtsac(T, obs_dim, act_dim, net_a.width, net_a.depth, net_c.width, net_c.depth,
                           config.num_critics, seed=seed)
         eng.set_params(L.ACTOR, a)
@@ -192,6 +254,7 @@ class MTSAC(OffPolicyAlgorithm):
         agent = MTSAC(config, env_config, seed, eng, kw)
         agent.pcgrad = pcgrad
         agent.cagrad = cagrad
+        agent.gradnorm = gradnorm
         return agent
 
     def _rebuild(self, **changes) -> None:
@@ -204,6 +267,7 @@ class MTSAC(OffPolicyAlgorithm):
         keep = {w: self.engine.get_params(w) for w in range(10)}
         counts = [self.engine.get_adam_count(i) for i in range(3)]
         noise = self.engine.noise_state()
+        gn_state = [self.engine.gradnorm_state(w) for w in range(2)] if self.gradnorm else []
         self._cfg_kwargs.update(changes)
         old = self.engine
         self.engine = MTSACEngine(make_config(**self._cfg_kwargs), device=old.device)
@@ -212,6 +276,10 @@ class MTSAC(OffPolicyAlgorithm):
             self.engine.set_pcgrad(True, self.config.actor_config.network_config.optimizer.cosine_sim_logs)
         if self.cagrad:
             self.engine.set_cagrad(True)
+        if self.gradnorm:  # re-initialised by the switch; the state so far is carried over
+            self.engine.set_gradnorm(True, **_gradnorm_args(self.config))
+            for w, st in enumerate(gn_state):
+                self.engine.set_gradnorm_state(w, st)
         for w, v in keep.items():
             self.engine.set_params(w, v)
         for i, c in enumerate(counts):
@@ -268,13 +336,13 @@ class MTSAC(OffPolicyAlgorithm):
         if n != self._cfg_kwargs["batch_per_task"]:  # raises once a buffer lives in the engine
             self._rebuild(batch_per_task=n, capacity=max(self._cfg_kwargs["capacity"], n))
         self.engine.update(tuple(data))
-        return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad)
+        return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad, self.gradnorm)
 
     def update_from_buffer(self, replay_buffer, batch_size: int, want_logs: bool):
         if getattr(replay_buffer, "engine", None) is self.engine and batch_size // self.num_tasks == \
                 self._cfg_kwargs["batch_per_task"]:
             self.engine.update_many(1)  # device sampling + update, no host round trip
-            return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad)
+            return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad, self.gradnorm)
         return super().update_from_buffer(replay_buffer, batch_size, want_logs)
 
     def compute_weights(self, data):

@@ -2070,7 +2070,12 @@ struct mtsac_engine {
   //
   // CAGrad (CAGradConfig: cagrad -> clip_by_global_norm -> adam; mtrl/optim/cagrad.py) is the same step
   // with another solve between the Gram and the combine (cagrad.hip): `surgery` picks it.
-  enum { SURGERY_NONE = 0, SURGERY_PCGRAD = 1, SURGERY_CAGRAD = 2 };
+  //
+  // GradNorm (GradNormConfig: gradnorm -> clip_by_global_norm -> adam; mtrl/optim/gradnorm.py) is the same
+  // step again (gradnorm.hip): it also consumes the per-task loss values (task_losses over the split
+  // passes' per-row terms) and carries state from step to step -- task weights, latched first losses and
+  // the inner Adam's moments on the device, the inner count here.
+  enum { SURGERY_NONE = 0, SURGERY_PCGRAD = 1, SURGERY_CAGRAD = 2, SURGERY_GRADNORM = 3 };
   static constexpr int CA_MAX_ITERS = 1024;  // obj_hist slots per network
   int surgery = SURGERY_NONE;
   bool pc_cos = false, pc_pinned = false, pc_graph_before = true;
@@ -2082,6 +2087,11 @@ struct mtsac_engine {
   bool ca_cos = false;
   float* ca_tw = nullptr;                        // [2][64] task weights
   double *ca_hist = nullptr, *ca_w0 = nullptr;   // [2][CA_MAX_ITERS] objectives, [64] a kernel-alone start
+  // GradNorm: slot 0 critic, 1 actor, 2 the kernel-alone call's
+  float *gn_state = nullptr, *gn_loss = nullptr;  // [3][4][64] task_weights, original_losses, mu, nu; [3][64]
+  long long gn_count[2] = {0, 0};                 // inner Adam counts
+  double gn_asym = 0.12, gn_lr[2] = {3e-4, 3e-4}, gn_eps[2] = {1e-5, 1e-5}, gn_max_norm[2] = {1.0, 1.0};
+  bool gn_clip[2] = {true, true}, gn_weighted = false, gn_ready = false;  // ready: initialised once
 
   int ensure_pcgrad_buffers() {
     int rc = 0;
@@ -2089,7 +2099,8 @@ struct mtsac_engine {
     if ((rc = alloc(&pc_gram, 64 * 64)) || (rc = alloc(&pc_c, 64 * 64)) || (rc = alloc(&pc_w, 2 * 64)) ||
         (rc = alloc(&pc_logs, 2 * 8)) || (rc = alloc(&pc_row_e, (size_t)B)) || (rc = alloc(&pc_perm, 2 * 64)) ||
         (rc = alloc(&pc_pin, 2 * 64)) || (rc = alloc(&ca_tw, 2 * 64)) ||
-        (rc = alloc(&ca_hist, 2 * (size_t)CA_MAX_ITERS)) || (rc = alloc(&ca_w0, 64)))
+        (rc = alloc(&ca_hist, 2 * (size_t)CA_MAX_ITERS)) || (rc = alloc(&ca_w0, 64)) ||
+        (rc = alloc(&gn_state, 3 * 4 * 64)) || (rc = alloc(&gn_loss, 3 * 64)))
       return rc;
     return hipDeviceSynchronize() == hipSuccess ? 0 : fail(-5, "device synchronize");
   }
@@ -2144,11 +2155,48 @@ struct mtsac_engine {
     cagrad_solve(s, cur);
   }
 
+  // GradNorm's solve on pc_gram with the state and losses of slot `slot`: combine weights into the pc_w
+  // slot of network w, gradnorm_loss and |mean_t g_t| into its pc_logs slot; count: the advanced one
+  void gn_solve_of(int w, int slot, double asymmetry, bool clip, double lr, double eps, double max_norm,
+                   bool weighted, long long count) {
+    GradnormSolve s{};
+    s.gram = pc_gram;
+    s.T = T_l;
+    s.losses = gn_loss + 64 * slot;
+    s.asymmetry = asymmetry;
+    s.per_task_clip = clip ? 1 : 0;
+    s.lr = lr;
+    s.eps = eps;
+    s.max_norm = max_norm;
+    s.weighted = weighted ? 1 : 0;
+    s.count = count;
+    float* stt = gn_state + 4 * 64 * slot;
+    s.task_weights = stt;
+    s.original_losses = stt + 64;
+    s.mu = stt + 128;
+    s.nu = stt + 192;
+    s.w = pc_w + 64 * w;
+    s.logs = pc_logs + 8 * w;
+    gradnorm_solve(s, cur);
+  }
+
+  // the per-task loss values of network w from the split pass's per-row terms: the critic's row_a (sum over
+  // the ensemble of the squared TD errors) over E n, the actor's row_c (alpha logpi - min Q, the explore
+  // term taken off by action_grad) over n
+  void gn_losses_of(int w) {
+    const int n_rows = B / T_l;
+    if (w == 0) task_losses(row_a, T_l, n_rows, 1.0 / ((double)critic.E * (double)n_rows), gn_loss, cur);
+    else task_losses(row_c, T_l, n_rows, 1.0 / (double)n_rows, gn_loss + 64, cur);
+  }
+
   // Gram, solve, combine of network w (0 critic, 1 actor): Net::g = mean_i g_i^pc (PCGrad), or CAGrad's
-  // update
+  // or GradNorm's update
   void pc_surgery(Net& net, int w) {
+    if (surgery == SURGERY_GRADNORM) gn_losses_of(w);
     pc_gram_of(w);
-    if (surgery == SURGERY_CAGRAD) ca_solve_of(w, ca_c, ca_iters, ca_lr, ca_momentum, nullptr, ca_cos);
+    if (surgery == SURGERY_GRADNORM)
+      gn_solve_of(w, w, gn_asym, gn_clip[w], gn_lr[w], gn_eps[w], gn_max_norm[w], gn_weighted, ++gn_count[w]);
+    else if (surgery == SURGERY_CAGRAD) ca_solve_of(w, ca_c, ca_iters, ca_lr, ca_momentum, nullptr, ca_cos);
     else pc_solve_of(w, pc_pinned ? pc_pin + 64 * w : nullptr, pc_cos);
     task_combine(tg[w], pc_w + 64 * w, T_l, tgP[w], pc_leaves(net), net.g, cur);
   }
@@ -3062,7 +3110,7 @@ int mtsac_update(mtsac_engine* h, const mtsac_batch* b, const float* eps_next, c
   }
   h->tl_next = 0;
   if (h->surgery) {
-    if (h->sharded()) return fail(-95, "PCGrad / CAGrad needs every task on one engine (unsharded)");
+    if (h->sharded()) return fail(-95, "PCGrad / CAGrad / GradNorm needs every task on one engine (unsharded)");
     h->pcgrad_step(b == nullptr, eps_next == nullptr);
   } else {
     h->step(b == nullptr, eps_next == nullptr);
@@ -3199,6 +3247,8 @@ int mtsac_set_pcgrad(mtsac_engine* h, int32_t on, int32_t cosine_sim_logs) {
     return 0;
   }
   if (h->surgery == mtsac_engine::SURGERY_CAGRAD) return fail(-16, "CAGrad is on (mtsac_set_cagrad(0) first)");
+  if (h->surgery == mtsac_engine::SURGERY_GRADNORM)
+    return fail(-16, "GradNorm is on (mtsac_set_gradnorm(0) first)");
   if (h->T_l != h->T_g || h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
   if (h->cfg.use_task_weights)
     return fail(-95, "PCGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
@@ -3341,6 +3391,8 @@ int mtsac_set_cagrad(mtsac_engine* h, int32_t on, double c, int32_t num_iteratio
     return 0;
   }
   if (h->surgery == mtsac_engine::SURGERY_PCGRAD) return fail(-16, "PCGrad is on (mtsac_set_pcgrad(0) first)");
+  if (h->surgery == mtsac_engine::SURGERY_GRADNORM)
+    return fail(-16, "GradNorm is on (mtsac_set_gradnorm(0) first)");
   if (h->T_l != h->T_g || h->sharded()) return fail(-95, "CAGrad needs every task on one engine (unsharded)");
   if (h->cfg.use_task_weights)
     return fail(-95, "CAGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
@@ -3407,12 +3459,192 @@ int mtsac_task_cagrad_solve(mtsac_engine* h, int which, double c, int32_t num_it
   return 0;
 }
 
+// ---------------------------------------------------------------- GradNorm
+static int gradnorm_args(double asymmetry, const double* lr, const double* eps, const double* max_norm, int nets) {
+  if (!std::isfinite(asymmetry)) return fail(-22, "GradNorm: asymmetry must be finite");
+  for (int w = 0; w < nets; ++w) {
+    if (!std::isfinite(lr[w]) || !std::isfinite(eps[w])) return fail(-22, "GradNorm: inner lr and eps must be finite");
+    if (std::isnan(max_norm[w]) || std::isinf(max_norm[w]))
+      return fail(-22, "GradNorm: inner max_grad_norm must be finite (negative: none)");
+  }
+  return 0;
+}
+
+int mtsac_set_gradnorm(mtsac_engine* h, int32_t on, double asymmetry, const int32_t* per_task_clip,
+                       const double* inner_lr, const double* inner_eps, const double* inner_max_grad_norm,
+                       const float* initial_weights, int32_t weighted_norms) {
+  if (!h) return fail(-22, "null engine");
+  if (!on) {
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (h->surgery == mtsac_engine::SURGERY_GRADNORM) {
+      h->use_graph = h->pc_graph_before;
+      h->surgery = mtsac_engine::SURGERY_NONE;
+    }
+    return 0;
+  }
+  if (h->surgery == mtsac_engine::SURGERY_PCGRAD) return fail(-16, "PCGrad is on (mtsac_set_pcgrad(0) first)");
+  if (h->surgery == mtsac_engine::SURGERY_CAGRAD) return fail(-16, "CAGrad is on (mtsac_set_cagrad(0) first)");
+  if (h->T_l != h->T_g || h->sharded()) return fail(-95, "GradNorm needs every task on one engine (unsharded)");
+  if (h->cfg.use_task_weights)
+    return fail(-95, "GradNorm with use_task_weights: the reference's split losses multiply by the unsplit weights");
+  if (h->T_l > 64) return fail(-22, "GradNorm: at most 64 tasks");
+  if (!per_task_clip || !inner_lr || !inner_eps || !inner_max_grad_norm) return fail(-22, "null argument");
+  int rc = gradnorm_args(asymmetry, inner_lr, inner_eps, inner_max_grad_norm, 2);
+  if (rc) return rc;
+  // init (gradnorm.py:70-84): the weights normalised to sum T in fp32, the first losses +inf, Adam zeros
+  const int T = h->T_l;
+  std::vector<float> stt(2 * 4 * 64, 0.f);
+  for (int w = 0; w < 2; ++w) {
+    float* tw = stt.data() + 4 * 64 * w;
+    float sum = 0.f;
+    for (int t = 0; t < T; ++t) {
+      tw[t] = initial_weights ? initial_weights[w * T + t] : 1.f;
+      if (!std::isfinite(tw[t])) return fail(-22, "GradNorm: initial_weights must be finite");
+      sum += tw[t];
+    }
+    if (sum == 0.f || !std::isfinite(sum)) return fail(-22, "GradNorm: initial_weights sum to zero");
+    for (int t = 0; t < T; ++t) {
+      tw[t] = (tw[t] / sum) * (float)T;
+      tw[64 + t] = INFINITY;
+    }
+  }
+  if ((rc = h->ensure_task_grad_buffers())) return rc;
+  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  HIP_TRY(hipStreamSynchronize(h->st));
+  if (h->gexec) {  // a captured plain step is not this mode's step
+    (void)hipGraphExecDestroy(h->gexec);
+    (void)hipGraphDestroy(h->graph);
+    h->gexec = nullptr;
+    h->graph = nullptr;
+  }
+  HIP_TRY(hipMemcpy(h->gn_state, stt.data(), sizeof(float) * stt.size(), hipMemcpyHostToDevice));
+  if (!h->surgery) h->pc_graph_before = h->use_graph;
+  h->use_graph = false;
+  h->surgery = mtsac_engine::SURGERY_GRADNORM;
+  h->gn_asym = asymmetry;
+  h->gn_weighted = weighted_norms != 0;
+  h->gn_ready = true;
+  for (int w = 0; w < 2; ++w) {
+    h->gn_clip[w] = per_task_clip[w] != 0;
+    h->gn_lr[w] = inner_lr[w];
+    h->gn_eps[w] = inner_eps[w];
+    h->gn_max_norm[w] = inner_max_grad_norm[w] < 0.0 ? -1.0 : inner_max_grad_norm[w];
+    h->gn_count[w] = 0;
+  }
+  return 0;
+}
+
+static int gradnorm_slot(mtsac_engine* h, int which) {
+  if (!h) return fail(-22, "null engine");
+  if (which != 0 && which != 1) return fail(-22, "which: 0 critic, 1 actor");
+  if (!h->gn_ready) return fail(-22, "GradNorm is not set up (mtsac_set_gradnorm)");
+  return 0;
+}
+
+int mtsac_gradnorm_get_state(mtsac_engine* h, int which, float* task_weights, float* original_losses, float* mu,
+                             float* nu, int64_t* count) {
+  if (int rc = gradnorm_slot(h, which)) return rc;
+  if (!task_weights || !original_losses || !mu || !nu || !count) return fail(-22, "null argument");
+  float stt[4 * 64];
+  HIP_TRY(hipMemcpyAsync(stt, h->gn_state + 4 * 64 * which, sizeof(stt), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  float* outs[4] = {task_weights, original_losses, mu, nu};
+  for (int k = 0; k < 4; ++k)
+    for (int t = 0; t < h->T_l; ++t) outs[k][t] = stt[64 * k + t];
+  *count = h->gn_count[which];
+  return h->check_err();
+}
+
+int mtsac_gradnorm_set_state(mtsac_engine* h, int which, const float* task_weights, const float* original_losses,
+                             const float* mu, const float* nu, int64_t count) {
+  if (int rc = gradnorm_slot(h, which)) return rc;
+  if (!task_weights || !original_losses || !mu || !nu || count < 0) return fail(-22, "bad argument");
+  float stt[4 * 64] = {};
+  const float* ins[4] = {task_weights, original_losses, mu, nu};
+  for (int k = 0; k < 4; ++k)
+    for (int t = 0; t < h->T_l; ++t) stt[64 * k + t] = ins[k][t];
+  HIP_TRY(hipStreamSynchronize(h->st));
+  HIP_TRY(hipMemcpy(h->gn_state + 4 * 64 * which, stt, sizeof(stt), hipMemcpyHostToDevice));
+  h->gn_count[which] = count;
+  return 0;
+}
+
+int mtsac_get_gradnorm_logs(mtsac_engine* h, float* out) {
+  if (int rc = gradnorm_slot(h, 0)) return rc;
+  if (!out) return fail(-22, "null argument");
+  float l[16], stt[2 * 4 * 64];
+  HIP_TRY(hipMemcpyAsync(l, h->pc_logs, sizeof(l), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(stt, h->gn_state, sizeof(stt), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  const int T = h->T_l;
+  for (int w = 0; w < 2; ++w) {
+    float* o = out + (2 * T + 1) * w;
+    for (int t = 0; t < T; ++t) {
+      o[t] = stt[4 * 64 * w + t];
+      o[T + t] = stt[4 * 64 * w + 64 + t];
+    }
+    o[2 * T] = l[8 * w];
+  }
+  return h->check_err();
+}
+
+int mtsac_get_gradnorm_task_losses(mtsac_engine* h, float* out) {
+  if (int rc = gradnorm_slot(h, 0)) return rc;
+  if (!out) return fail(-22, "null argument");
+  float l[2 * 64];
+  HIP_TRY(hipMemcpyAsync(l, h->gn_loss, sizeof(l), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  for (int w = 0; w < 2; ++w)
+    for (int t = 0; t < h->T_l; ++t) out[h->T_l * w + t] = l[64 * w + t];
+  return h->check_err();
+}
+
+int mtsac_task_gradnorm_solve(mtsac_engine* h, int which, const float* task_losses, double asymmetry,
+                              int32_t per_task_clip, double inner_lr, double inner_eps, double inner_max_grad_norm,
+                              int32_t weighted_norms, float* task_weights, float* original_losses, float* mu,
+                              float* nu, int64_t* count, float* w, float* logs) {
+  int rc = task_grad_ready(h, which);
+  if (rc) return rc;
+  if (!task_losses || !task_weights || !original_losses || !mu || !nu || !count || !w || !logs)
+    return fail(-22, "null argument");
+  if (h->T_l > 64) return fail(-22, "GradNorm: at most 64 tasks");
+  if (*count < 0) return fail(-22, "GradNorm: negative count");
+  if ((rc = gradnorm_args(asymmetry, &inner_lr, &inner_eps, &inner_max_grad_norm, 1))) return rc;
+  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  const int T = h->T_l;
+  float stt[4 * 64] = {}, ls[64] = {};
+  float* io[4] = {task_weights, original_losses, mu, nu};
+  for (int k = 0; k < 4; ++k)
+    for (int t = 0; t < T; ++t) stt[64 * k + t] = io[k][t];
+  for (int t = 0; t < T; ++t) ls[t] = task_losses[t];
+  HIP_TRY(hipStreamSynchronize(h->st));
+  HIP_TRY(hipMemcpy(h->gn_state + 4 * 64 * 2, stt, sizeof(stt), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->gn_loss + 64 * 2, ls, sizeof(ls), hipMemcpyHostToDevice));
+  h->cur = h->st;
+  h->pc_gram_of(which);
+  h->gn_solve_of(which, 2, asymmetry, per_task_clip != 0, inner_lr, inner_eps,
+                 inner_max_grad_norm < 0.0 ? -1.0 : inner_max_grad_norm, weighted_norms != 0, *count + 1);
+  HIP_TRY(hipGetLastError());
+  float lg[8];
+  HIP_TRY(hipMemcpyAsync(stt, h->gn_state + 4 * 64 * 2, sizeof(stt), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(w, h->pc_w + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(lg, h->pc_logs + 8 * which, sizeof(lg), hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  for (int k = 0; k < 4; ++k)
+    for (int t = 0; t < T; ++t) io[k][t] = stt[64 * k + t];
+  *count += 1;
+  logs[0] = lg[0];
+  logs[1] = lg[1];
+  logs[2] = lg[5];
+  return 0;
+}
+
 int mtsac_update_many(mtsac_engine* h, int32_t steps) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
   if (steps <= 0) return 0;
   if (h->surgery) {  // eager, one stream, no overlap between steps; PCGrad's task orders are drawn on the device
-    if (h->sharded()) return fail(-95, "PCGrad / CAGrad needs every task on one engine (unsharded)");
+    if (h->sharded()) return fail(-95, "PCGrad / CAGrad / GradNorm needs every task on one engine (unsharded)");
     h->tl_next = 0;
     for (int s = 0; s < steps; ++s) h->pcgrad_step(true, true);
     HIP_TRY(hipGetLastError());
@@ -3461,7 +3693,7 @@ int mtsac_get_logs(mtsac_engine* h, float* logs) {
 int mtsac_enable_graph(mtsac_engine* h, int32_t enable) {
   if (!h) return fail(-22, "null engine");
   if (enable && h->surgery)
-    return fail(-95, "the PCGrad / CAGrad step is not captured: graph replay is unavailable in this mode");
+    return fail(-95, "the PCGrad / CAGrad / GradNorm step is not captured: graph replay is unavailable in this mode");
   h->use_graph = enable != 0;
   return 0;
 }

@@ -673,6 +673,35 @@ struct CagradSolve {
 };
 void cagrad_solve(const CagradSolve& s, hipStream_t st);
 
+// ------------------------------------------------------------------ GradNorm in Gram form (gradnorm.hip;
+// mtrl/optim/gradnorm.py).  task_losses: out[t] = inv * sum_i row[i * T + t], i = 0 .. n - 1 in order, fp64
+// accumulation (the per-task loss values of the split passes' per-row terms).  gradnorm_solve: one
+// wavefront on the Gram matrix task_gram left, the task losses and the state carried from step to step:
+// per-task clip to norm 1 (optional), latch of the first losses, the rates, the loss on the task norms and
+// (weighted form only) its gradient with respect to the task weights, the inner [clip +] Adam step on them
+// (on a zero gradient in the reference form, so that the count advances as optax's does), the fp32
+// renormalisation to sum T, and the combine weights w_t s_t on the RAW rows for task_combine.
+struct GradnormSolve {
+  const double* gram;      // [T*T]
+  int T;
+  const float* losses;     // [T] per-task loss values of this step
+  double asymmetry;
+  int per_task_clip;       // bool(GradNormConfig.max_grad_norm): rows clipped to norm 1.0
+  double lr, eps;          // inner Adam
+  double max_norm;         // inner clip_by_global_norm; negative: none
+  int weighted;            // the weighted-norm (paper) form; 0: the reference's, gradient exactly zero
+  long long count;         // inner Adam's count AFTER this step
+  float* task_weights;     // [T] state, read and written
+  float* original_losses;  // [T]
+  float* mu;               // [T]
+  float* nu;               // [T]
+  float* w;                // [T] combine weights
+  float* logs;             // [8]: 0 gradnorm_loss, 1 sign margin min_t |d_t| / mean(n), 5 |mean_t g_t| (the
+                           // pre-surgery norm, where pcgrad_logs reads it)
+};
+void task_losses(const float* row, int T, int n, double inv, float* out, hipStream_t st);
+void gradnorm_solve(const GradnormSolve& s, hipStream_t st);
+
 // sets what mtsac_last_error returns on this thread (engine.cpp; the debug entry points name a
 // written guard band through it)
 void set_last_error(const char* msg);

@@ -22,6 +22,9 @@ PCGRAD_LOG_KEYS = ("n_grad_conflicts", "avg_grad_magnitude", "avg_grad_magnitude
 # task_weights
 CAGRAD_LOG_KEYS = ("task_weights", "avg_grad_magnitude", "avg_grad_magnitude_before_surgery",
                    "avg_cosine_similarity", "cagrad_objective")
+# GradNormState fields the reference logs (mtrl/optim/gradnorm.py:34-37, mtsac.py:1224-1239): arrays of
+# length T; the inner opt_state lives in the checkpoint, not in the logs
+GRADNORM_LOG_KEYS = ("task_weights", "original_losses")
 
 
 def _ptr(x) -> tuple[int, Any]:
@@ -338,6 +341,90 @@ class MTSACEngine:
         logs.update({k: float(v) for k, v in zip(CAGRAD_LOG_KEYS[1:], lg[:4])})
         logs.update(best_iteration=int(lg[4]), grad_magnitude=float(lg[5]), obj_hist=hist)
         return w, logs
+
+    # ------------------------------------------------------------------ GradNorm (include/mtsac.h)
+    @staticmethod
+    def _pair(v, dtype, none=None):
+        """A per-network value (critic, actor) from a scalar or a pair; None -> ``none``."""
+        v = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else (v, v)
+        return np.array([none if x is None else x for x in v], dtype).reshape(2)
+
+    def set_gradnorm(self, on: bool, asymmetry: float = 0.12, per_task_clip=True, inner_lr=3e-4, inner_eps=1e-5,
+                     inner_max_grad_norm=1.0, initial_weights=None, weighted_norms: bool = False) -> None:
+        """GradNorm on both optimizers: update / update_many run the GradNorm step, from a freshly
+        initialised state.  ``per_task_clip`` (bool(GradNormConfig.max_grad_norm)), ``inner_lr``,
+        ``inner_eps`` and ``inner_max_grad_norm`` (None: no clip) are scalars or (critic, actor) pairs;
+        ``initial_weights``: None (ones), [T] for both networks or [2][T].  ``weighted_norms``: the form the
+        reference has commented out (mtrl_amd/gradnorm.py)."""
+        T = self.T_l
+        clip = self._pair(per_task_clip, np.int32)
+        lr, eps = self._pair(inner_lr, np.float64), self._pair(inner_eps, np.float64)
+        mx = self._pair(inner_max_grad_norm, np.float64, none=-1.0)
+        iw = None
+        if initial_weights is not None:
+            iw = np.ascontiguousarray(np.broadcast_to(np.asarray(initial_weights, np.float32), (2, T)))
+        check(self.lib.mtsac_set_gradnorm(self._h, 1 if on else 0, float(asymmetry), clip.ctypes.data, lr.ctypes.data,
+                                          eps.ctypes.data, mx.ctypes.data, None if iw is None else iw.ctypes.data,
+                                          1 if weighted_norms else 0))
+
+    def gradnorm_state(self, which: int):
+        """The ``mtrl_amd.gradnorm.GradNormState`` of one network (0 critic, 1 actor)."""
+        from .gradnorm import GradNormState
+
+        T = self.T_l
+        a = [np.empty(T, np.float32) for _ in range(4)]
+        n = ctypes.c_int64(0)
+        check(self.lib.mtsac_gradnorm_get_state(self._h, which, *(x.ctypes.data for x in a), ctypes.addressof(n)))
+        return GradNormState(task_weights=a[0], original_losses=a[1], count=int(n.value), mu=a[2], nu=a[3])
+
+    def set_gradnorm_state(self, which: int, state) -> None:
+        a = [np.ascontiguousarray(x, np.float32).reshape(self.T_l)
+             for x in (state.task_weights, state.original_losses, state.mu, state.nu)]
+        check(self.lib.mtsac_gradnorm_set_state(self._h, which, *(x.ctypes.data for x in a), int(state.count)))
+
+    def gradnorm_logs(self) -> dict:
+        """``metrics/{critic,actor}_{task_weights,original_losses}`` (float32 arrays of length T) and
+        ``metrics/{critic,actor}_gradnorm_loss``."""
+        T = self.T_l
+        out = np.empty(2 * (2 * T + 1), np.float32)
+        check(self.lib.mtsac_get_gradnorm_logs(self._h, out.ctypes.data))
+        logs = {}
+        for w, net in enumerate(("critic", "actor")):
+            o = (2 * T + 1) * w
+            logs[f"metrics/{net}_task_weights"] = out[o:o + T].copy()
+            logs[f"metrics/{net}_original_losses"] = out[o + T:o + 2 * T].copy()
+            logs[f"metrics/{net}_gradnorm_loss"] = float(out[o + 2 * T])
+        return logs
+
+    def gradnorm_task_losses(self) -> np.ndarray:
+        """[2][T]: the per-task loss values the last GradNorm step's solves read (critic, actor)."""
+        out = np.empty((2, self.T_l), np.float32)
+        check(self.lib.mtsac_get_gradnorm_task_losses(self._h, out.ctypes.data))
+        return out
+
+    def task_gradnorm_solve(self, which: int, task_losses, state, asymmetry: float = 0.12, per_task_clip: bool = True,
+                            inner_lr: float = 3e-4, inner_eps: float = 1e-5, inner_max_grad_norm: float | None = 1.0,
+                            weighted_norms: bool = False):
+        """(w [T] float32 combine weights on the raw rows, new GradNormState, logs) of the device solve on
+        the matrix set_task_gradients / task_gradients left; the arguments of
+        ``mtrl_amd.gradnorm.gradnorm_from_gram``.  logs: task_weights, original_losses, gradnorm_loss,
+        sign_margin, grad_magnitude."""
+        from .gradnorm import GradNormState
+
+        T = self.T_l
+        ls = np.ascontiguousarray(task_losses, np.float32).reshape(T)
+        a = [np.array(x, np.float32).reshape(T) for x in (state.task_weights, state.original_losses, state.mu, state.nu)]
+        n = ctypes.c_int64(int(state.count))
+        w, lg = np.empty(T, np.float32), np.empty(3, np.float32)
+        check(self.lib.mtsac_task_gradnorm_solve(
+            self._h, which, ls.ctypes.data, float(asymmetry), 1 if per_task_clip else 0, float(inner_lr),
+            float(inner_eps), -1.0 if inner_max_grad_norm is None else float(inner_max_grad_norm),
+            1 if weighted_norms else 0, *(x.ctypes.data for x in a), ctypes.addressof(n), w.ctypes.data,
+            lg.ctypes.data))
+        new = GradNormState(task_weights=a[0], original_losses=a[1], count=int(n.value), mu=a[2], nu=a[3])
+        logs = {"task_weights": a[0], "original_losses": a[1], "gradnorm_loss": float(lg[0]),
+                "sign_margin": float(lg[1]), "grad_magnitude": float(lg[2])}
+        return w, new, logs
 
     def update_many(self, steps: int) -> None:
         check(self.lib.mtsac_update_many(self._h, steps))

@@ -18,6 +18,9 @@ gram_kernel / combine_kernel (one launch per network per step) into achieved byt
 ``--surgery cagrad`` adds the CAGrad step on a third engine of the same tree: the
 three steps alternate within every repeat, ``--profile-steps`` runs CAGrad steps, and the kernel table
 lists cagrad_solve_kernel beside pcgrad_solve_kernel.
+``--surgery gradnorm`` does the same with the GradNorm step as a fourth engine: plain,
+PCGrad, CAGrad and GradNorm alternate within every repeat, and the kernel table lists gradnorm_solve_kernel
+and task_losses_kernel too.
 Needs the GPU (except --stats-csv): there is no fallback.
 """
 
@@ -48,7 +51,7 @@ def param_counts(T, W, depth=3, A=4, E=2):
 
 
 def make_engine(T, W, n, precision, surgery):
-    """surgery: None (the plain eager step), "pcgrad" or "cagrad"."""
+    """surgery: None (the plain eager step), "pcgrad", "cagrad" or "gradnorm"."""
     from mtrl_amd import _lib as L
     from mtrl_amd.engine import MTSACEngine, make_config
     from mtrl_amd.init import init_mtsac
@@ -63,7 +66,7 @@ def make_engine(T, W, n, precision, surgery):
     e.seed_rng(1)
     e.enable_graph(False)
     if surgery:
-        e.set_pcgrad(True) if surgery == "pcgrad" else e.set_cagrad(True)
+        {"pcgrad": e.set_pcgrad, "cagrad": e.set_cagrad, "gradnorm": e.set_gradnorm}[surgery](True)
         assert (e.task_gradient_size(0), e.task_gradient_size(1)) == param_counts(T, W)
     return e
 
@@ -90,7 +93,7 @@ def kernel_rates(stats_csv, T, W):
     with open(stats_csv, newline="") as f:
         for row in csv.DictReader(f):
             for key in ("gram_kernel", "combine_kernel", "gram_sum_kernel", "pcgrad_solve_kernel",
-                        "cagrad_solve_kernel"):
+                        "cagrad_solve_kernel", "gradnorm_solve_kernel", "task_losses_kernel"):
                 if f"::{key}" in row["Name"] or row["Name"].startswith(key):
                     avg = float(row["AverageNs"]) * 1e-9
                     out[key] = {"calls": int(row["Calls"]), "avg_us": 1e6 * avg}
@@ -106,8 +109,9 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--surgery", default="pcgrad", choices=["pcgrad", "cagrad"],
-                    help="cagrad: time the CAGrad step too, alternating with the other two")
+    ap.add_argument("--surgery", default="pcgrad", choices=["pcgrad", "cagrad", "gradnorm"],
+                    help="cagrad: time the CAGrad step too, alternating with the other two; gradnorm: the CAGrad "
+                         "and the GradNorm step too")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="only run this many steps of --surgery's kind (for rocprofv3)")
     ap.add_argument("--stats-csv", default=None, help="rocprofv3 kernel-stats CSV of a --profile-steps run")
@@ -126,17 +130,22 @@ def main():
             continue
         pc = make_engine(T, W, n, args.precision, "pcgrad")
         plain = make_engine(T, W, n, args.precision, None)
-        ca = make_engine(T, W, n, args.precision, "cagrad") if args.surgery == "cagrad" else None
+        ca = make_engine(T, W, n, args.precision, "cagrad") if args.surgery in ("cagrad", "gradnorm") else None
+        gn = make_engine(T, W, n, args.precision, "gradnorm") if args.surgery == "gradnorm" else None
         plain.update_many(args.warmup)
         pc.update_many(args.warmup)
         if ca:
             ca.update_many(args.warmup)
-        tp, tq, tc = [], [], []
+        if gn:
+            gn.update_many(args.warmup)
+        tp, tq, tc, tg = [], [], [], []
         for _ in range(args.repeats):
             tp.append(time_steps(plain, args.steps))
             tq.append(time_steps(pc, args.steps))
             if ca:
                 tc.append(time_steps(ca, args.steps))
+            if gn:
+                tg.append(time_steps(gn, args.steps))
         logs = pc.logs() | pc.pcgrad_logs()
         if ca:
             logs |= {k: v for k, v in ca.cagrad_logs().items() if np.ndim(v) == 0}
@@ -150,6 +159,12 @@ def main():
         if ca:
             out |= {"cagrad_step": spread(tc), "ratio_cagrad_over_pcgrad": statistics.median(tc) / statistics.median(tq)}
             ca.close()
+        if gn:
+            st = [gn.gradnorm_state(w) for w in range(2)]
+            out |= {"gradnorm_step": spread(tg), "ratio_gradnorm_over_cagrad": statistics.median(tg) / statistics.median(tc),
+                    "gradnorm_inner_counts": [s.count for s in st],
+                    "gradnorm_weights_finite": bool(all(np.all(np.isfinite(s.task_weights)) for s in st))}
+            gn.close()
         print(json.dumps(out), flush=True)
         plain.close()
         pc.close()
