@@ -124,6 +124,64 @@ int mtsac_debug_drq_c51(int B, int A, int Z, int ldh, const float* hc_s, const f
                         float gamma_n, float vmin, float vmax, float* m, int* a_next, float* q, float* dh,
                         float* loss_b, float* logit_b);
 
+/* Single SAC head kernels (heads.hip) on device 0, null stream, host pointers in and out, through the launch
+ * wrappers of kernels.h (so their dispatch by hd, A, W % 4 and rows per wave runs); 0 or a negative errno (-22
+ * for bad sizes, before anything is launched).  Outputs are guarded as the DrQ entries' are: an element a
+ * kernel left alone comes back NaN (float) or -1 (int), a written band returns -5.  Entries that take task[B]
+ * (local ids < T_l <= 64) build the per-task lists with task_rows on the device (row stride B) and return
+ * them: counts [T_l], rows [T_l][B] (-1 past counts[t]).  Tests only.
+ *
+ * The two launcher choices otherwise read once from the environment: rows per wave of the grouped policy
+ * heads and the action grad (1 / 2 / 4; anything else restores MTSAC_HEAD_RW / the choice by grid size), and
+ * head_backward_both's form (0 the fused kernel, 1 both passes in one launch; anything else restores
+ * MTSAC_HEAD_BWD_SPLIT / the choice by grid size).  Each returns the previous override (-1: none). */
+int mtsac_debug_head_rw(int rw);
+int mtsac_debug_head_bwd_split(int mode);
+/* policy_head: form 0 one wave per row (no lists), 1 grouped by task, 2 policy_head_pair on two row sets
+ * (h, eps and every output then hold two sets, [2][...]).  h [B][W], Wh [T_l][W][2A], bh [T_l][2A],
+ * eps [B][A] (injected noise, required).  flags bit 0: with WhT from head_transpose; bit 1 / bit 2: the
+ * action planes as split3 / split2h (at exponent 14), returned in planes [B][ld_a] as their unscaled sum.
+ * a_out, a_out2 [B][ld_a] (ld_a >= A: the columns past A stay NaN), logpi [B], cache [B][5A]. */
+int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
+                            const float* Wh, const float* bh, const float* eps, float ls_min, float ls_max,
+                            float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,
+                            int* rows);
+/* critic_head: mode 0 target, 1 critic, 2 actor; flags bit 0 fused_target (mode 1: th / tWh / tbh the target
+ * critic's head inputs, y_out written), bit 1 clip.  h [E][B][W], Wh [E][T_l][W], bh [E][T_l], log_alpha
+ * [T_glob], y [B] (mode 1 without fused_target), tw [B] or null.  Outputs y_out, row_a, row_b, alpha_w [B],
+ * dq [E][B] (what the mode does not write stays NaN), dq_amax [2048] the record's partial maxima and
+ * *dq_parts how many the launcher reports. */
+int mtsac_debug_head_critic(int mode, int flags, int B, int T_l, int E, int W, int T_glob, int task_begin,
+                            const int* task, const float* h, const float* Wh, const float* bh, const float* th,
+                            const float* tWh, const float* tbh, const float* rew, const float* done,
+                            const float* logpi, const float* log_alpha, const float* y, const float* tw, float gamma,
+                            float inv_norm, float* y_out, float* dq, float* row_a, float* row_b, float* alpha_w,
+                            float* dq_amax, int* dq_parts);
+/* active_rows of dq [E][B]: n [E], rows [E][B] (-1 past n[e]), slot [E][B]. */
+int mtsac_debug_head_active_rows(int E, int B, const float* dq, int* n, int* rows, int* slot);
+/* The head backward.  form 0: head_backward_data (only when W % 4 == 0, its contract) then
+ * head_backward_weight; form 1: head_backward_both; form 2: the compacted data pass (hd = 1, W % 4 == 0, planes:
+ * slot from active_rows on dq [E][B]; plane row s of member e is its s-th active row).  h [E][B][W],
+ * Wh [E][T_l][W][hd], dout [E][B][hd].  flags bit 0 / bit 1: split3 / split2h planes (bound inputs: max |dout|,
+ * max |Wh|, w_add 0, kmul hd), returned in planes [E][B][W] as their unscaled sum.  dz [E][B][W], dbp
+ * [E][4 T_l][W] and db [E][W] (colsum_finish of dbp), dWh [E][T_l][W][hd], dbh [E][T_l][hd].  info [8]: 0 whether
+ * the data pass / head_backward_both ran, 1 the split2h planes' exponent, 2 the self-check's fault word,
+ * 3.. n[e] (form 2). */
+int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W, int hd, const int* task, const float* h,
+                              const float* Wh, const float* dout, const float* dq, float* dz, float* dbp, float* db,
+                              float* planes, float* dWh, float* dbh, int* counts, int* rows, int* info);
+/* action_grad: dz1 [E][B][Wc] dense; with dq [E][B] (nullable) the rows are compacted by active_rows' slot
+ * first (the dense equivalent has zero rows where dq is 0).  W0 [E][Ic][Wc], cache [B][5A], alpha_w [B];
+ * a_data [B][ld_a_data] (nullable) with explore_scale and row_loss_in [B].  Outputs dout [B][2A], row_loss,
+ * row_explore [B] (NaN without a_data), dout_amax [2048] and *dout_parts as for the critic head. */
+int mtsac_debug_head_action_grad(int B, int E, int Wc, int Ic, int A, const float* dz1, const float* dq, const float* W0,
+                                 const float* cache, const float* alpha_w, const float* a_data, int ld_a_data,
+                                 float explore_scale, float ls_min, float ls_max, const float* row_loss_in, float* dout,
+                                 float* row_loss, float* row_explore, float* dout_amax, int* dout_parts);
+/* row_alpha: alpha_row [B] and, with use_tw, tw_row [B] (else left NaN) from log_alpha [T_glob]. */
+int mtsac_debug_head_row_alpha(int B, int T_l, int T_glob, int task_begin, int use_tw, const int* task,
+                               const float* log_alpha, float* alpha_row, float* tw_row);
+
 /* Eager update_many overlaps consecutive steps (the next gather and critic(s, a) forward beside
  * the previous actor backward / all-reduce / Adam): on = 1 always, 0 never (whole steps), -1 the
  * default (when the trunk gradients go through a device collective: RCCL or the modelled one).

@@ -182,6 +182,15 @@ SIGNATURES = {
     "mtsac_debug_drq_conv_path": (ctypes.c_int, [ctypes.c_int] * 6 + [P]),
     "mtsac_debug_drq_maxpool": (ctypes.c_int, [ctypes.c_int] * 4 + [P] * 5),
     "mtsac_debug_drq_c51": (ctypes.c_int, [ctypes.c_int] * 4 + [P] * 8 + [ctypes.c_float] * 3 + [P] * 6),
+    "mtsac_debug_head_rw": (ctypes.c_int, [ctypes.c_int]),
+    "mtsac_debug_head_bwd_split": (ctypes.c_int, [ctypes.c_int]),
+    "mtsac_debug_head_policy": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 5 + [ctypes.c_float] * 2 + [P] * 7),
+    "mtsac_debug_head_critic": (ctypes.c_int, [ctypes.c_int] * 8 + [P] * 13 + [ctypes.c_float] * 2 + [P] * 7),
+    "mtsac_debug_head_active_rows": (ctypes.c_int, [ctypes.c_int] * 2 + [P] * 4),
+    "mtsac_debug_head_backward": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 14),
+    "mtsac_debug_head_action_grad": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 6 + [ctypes.c_int] +
+                                     [ctypes.c_float] * 3 + [P] * 6),
+    "mtsac_debug_head_row_alpha": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 4),
     "mtsac_debug_set_pipeline": (ctypes.c_int, [P, I32]),
     "mtsac_debug_lane_mode": (ctypes.c_int, [P]),
     "mtsac_debug_opt_form": (ctypes.c_int, [P, ctypes.c_int]),

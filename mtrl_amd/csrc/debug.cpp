@@ -1,4 +1,4 @@
-// debug.cpp -- test-only entry points (include/mtsac_debug.h) for the plane GEMM.
+// debug.cpp -- test-only entry points (include/mtsac_debug.h): the plane GEMMs, the DrQ kernels, the SAC heads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -142,6 +142,57 @@ int sync_rc(const char* what) {
   if (e1 == hipSuccess && e2 == hipSuccess) return 0;
   set_last_error((std::string(what) + ": " + hipGetErrorString(e1 != hipSuccess ? e1 : e2)).c_str());
   return -5;
+}
+
+// ---- single SAC head kernels (heads.hip) ----
+// counts / rows of task[B] from task_rows on the device (row stride B), both guarded outputs
+struct TaskLists {
+  int* d_task = nullptr;
+  int* counts = nullptr;
+  int* rows = nullptr;
+  int max_count = 0;
+};
+bool tasks_ok(const int* task, int B, int T_l) {
+  if (!task || B < 1 || T_l < 1 || T_l > 64) return false;
+  for (int b = 0; b < B; ++b)
+    if (task[b] < 0 || task[b] >= T_l) return false;
+  return true;
+}
+TaskLists make_lists(Guarded& g, const int* task, int B, int T_l) {
+  TaskLists l;
+  std::vector<int> c(T_l, 0);
+  for (int b = 0; b < B; ++b) l.max_count = std::max(l.max_count, ++c[task[b]]);
+  l.d_task = g.in(task, (size_t)B);
+  l.counts = g.out<int>((size_t)T_l, "counts");
+  l.rows = g.out<int>((size_t)T_l * B, "rows");
+  if (g.ok) task_rows(l.d_task, B, T_l, l.counts, l.rows, B, nullptr);
+  return l;
+}
+// a guarded PlaneRec whose words start as all-ones (amax NaN); e set to `e`
+PlaneRec* rec_out(Guarded& g, int e, const char* name) {
+  PlaneRec* r = g.out<PlaneRec>(1, name);
+  if (r && hipMemcpy(&r->e, &e, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) g.ok = false;
+  return r;
+}
+// the unscaled sum of n elements' planes (16-bit words, plane stride ps): split3 h + m + l, split2h (h + l) 2^-e
+bool planes_sum(const __bf16* dev, size_t n_words, size_t ps, size_t n, bool h2, int e, float* out) {
+  std::vector<unsigned short> w(n_words);
+  if (hipMemcpy(w.data(), dev, n_words * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
+  for (size_t i = 0; i < n; ++i) {
+    if (h2) {
+      _Float16 a, b;
+      std::memcpy(&a, &w[i], 2);
+      std::memcpy(&b, &w[ps + i], 2);
+      out[i] = std::ldexp((float)a + (float)b, -e);
+    } else {
+      __bf16 a, b, c;
+      std::memcpy(&a, &w[i], 2);
+      std::memcpy(&b, &w[ps + i], 2);
+      std::memcpy(&c, &w[2 * ps + i], 2);
+      out[i] = ((float)a + (float)b) + (float)c;
+    }
+  }
+  return true;
 }
 
 }  // namespace
@@ -830,6 +881,301 @@ int mtsac_debug_drq_c51(int B, int A, int Z, int ldh, const float* hc_s, const f
                  g.back(dh, d_dh, nh) && g.back(loss_b, d_lb, (size_t)B) && g.back(logit_b, d_gb, (size_t)B)
              ? 0
              : -5;
+}
+
+int mtsac_debug_head_rw(int rw) {
+  const int old = g_head_rw;
+  g_head_rw = rw == 1 || rw == 2 || rw == 4 ? rw : -1;
+  return old;
+}
+
+int mtsac_debug_head_bwd_split(int mode) {
+  const int old = g_head_bwd_split;
+  g_head_bwd_split = mode == 0 || mode == 1 ? mode : -1;
+  return old;
+}
+
+int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
+                            const float* Wh, const float* bh, const float* eps, float ls_min, float ls_max,
+                            float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,
+                            int* rows) {
+  const bool whT = flags & 1, p3 = flags & 2, p2h = flags & 4;
+  if (form < 0 || form > 2 || (flags & ~7) || (p3 && p2h) || W < 1 || A < 1 || A > 4 || ld_a < A || !h || !Wh || !bh ||
+      !eps || !a_out || !a_out2 || !logpi || !cache || !counts || !rows || ((p3 || p2h) && !planes) ||
+      !tasks_ok(task, B, T_l) || (long long)B * W >= (1LL << 28))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const int hd = 2 * A, ns = form == 2 ? 2 : 1, H2E = 14;  // |a| <= 1 at 2^14 fits fp16
+  const size_t nw = (size_t)T_l * W * hd, npl = (p2h ? 2 : 3) * (size_t)B * ld_a;
+  Guarded g;
+  TaskLists tl = make_lists(g, task, B, T_l);
+  const float *d_h = g.in(h, (size_t)ns * B * W), *d_Wh = g.in(Wh, nw), *d_bh = g.in(bh, (size_t)T_l * hd);
+  const float* d_eps = g.in(eps, (size_t)ns * B * A);
+  float* d_WhT = whT ? g.out<float>(nw, "WhT") : nullptr;
+  PlaneRec* rec = p2h ? rec_out(g, H2E, "ap_rec") : nullptr;
+  float *d_a[2], *d_a2[2], *d_lp[2], *d_c[2];
+  __bf16* d_pl[2] = {nullptr, nullptr};
+  for (int s = 0; s < ns; ++s) {
+    d_a[s] = g.out<float>((size_t)B * ld_a, "a_out");
+    d_a2[s] = g.out<float>((size_t)B * ld_a, "a_out2");
+    d_lp[s] = g.out<float>((size_t)B, "logpi");
+    d_c[s] = g.out<float>((size_t)B * 5 * A, "cache");
+    if (p3 || p2h) d_pl[s] = g.out<__bf16>(npl, "a_planes");
+  }
+  if (!g.ok) return -12;
+  if (whT) head_transpose(d_Wh, T_l, W, hd, d_WhT, nullptr);
+  PolicyParams pp[2];
+  for (int s = 0; s < ns; ++s) {
+    PolicyParams p{};
+    p.head.h = d_h + (size_t)s * B * W; p.head.Wh = d_Wh; p.head.WhT = d_WhT; p.head.bh = d_bh; p.head.task = tl.d_task;
+    p.head.B = B; p.head.W = W; p.head.hd = hd; p.head.E = 1;
+    p.eps = d_eps + (size_t)s * B * A;
+    p.A = A; p.ls_min = ls_min; p.ls_max = ls_max;
+    p.a_out = d_a[s]; p.ld_a_out = ld_a; p.a_out2 = d_a2[s]; p.ld_a_out2 = ld_a;
+    p.a_planes = d_pl[s]; p.ap_ps = (long long)B * ld_a; p.ap_ld = ld_a; p.ap_rec = rec;
+    p.logpi = d_lp[s]; p.cache = d_c[s];
+    if (form != 0) {
+      p.counts = tl.counts; p.rows = tl.rows; p.max_rows = B; p.T_l = T_l; p.max_count = tl.max_count;
+    }
+    pp[s] = p;
+  }
+  if (form == 2) policy_head_pair(pp[0], pp[1], nullptr);
+  else policy_head(pp[0], nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("policy_head")) || (rc = g.check())) return rc;
+  for (int s = 0; s < ns; ++s) {
+    if (!g.back(a_out + (size_t)s * B * ld_a, d_a[s], (size_t)B * ld_a) ||
+        !g.back(a_out2 + (size_t)s * B * ld_a, d_a2[s], (size_t)B * ld_a) || !g.back(logpi + (size_t)s * B, d_lp[s], (size_t)B) ||
+        !g.back(cache + (size_t)s * B * 5 * A, d_c[s], (size_t)B * 5 * A))
+      return -5;
+    if (d_pl[s] && !planes_sum(d_pl[s], npl, (size_t)B * ld_a, (size_t)B * ld_a, p2h, H2E, planes + (size_t)s * B * ld_a))
+      return -5;
+  }
+  return g.back(counts, tl.counts, (size_t)T_l) && g.back(rows, tl.rows, (size_t)T_l * B) ? 0 : -5;
+}
+
+int mtsac_debug_head_critic(int mode, int flags, int B, int T_l, int E, int W, int T_glob, int task_begin,
+                            const int* task, const float* h, const float* Wh, const float* bh, const float* th,
+                            const float* tWh, const float* tbh, const float* rew, const float* done,
+                            const float* logpi, const float* log_alpha, const float* y, const float* tw, float gamma,
+                            float inv_norm, float* y_out, float* dq, float* row_a, float* row_b, float* alpha_w,
+                            float* dq_amax, int* dq_parts) {
+  const bool fused = flags & 1, clip = flags & 2;
+  if (mode < 0 || mode > 2 || (flags & ~3) || E < 1 || E > 4 || W < 1 || task_begin < 0 || T_glob < task_begin + T_l ||
+      !h || !Wh || !bh || !rew || !done || !logpi || !log_alpha || !y_out || !dq || !row_a || !row_b || !alpha_w ||
+      !dq_amax || !dq_parts || (fused && (mode != CH_CRITIC || !th || !tWh || !tbh)) ||
+      (mode == CH_CRITIC && !fused && !y) || !tasks_ok(task, B, T_l) || (long long)E * B * W >= (1LL << 28))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t nh = (size_t)E * B * W, nw = (size_t)E * T_l * W, nb = (size_t)E * T_l;
+  Guarded g;
+  const int* d_task = g.in(task, (size_t)B);
+  CriticHeadParams p{};
+  auto head = [&](const float* hh, const float* ww, const float* bb) {
+    HeadParams q{};
+    q.h = g.in(hh, nh); q.Wh = g.in(ww, nw); q.bh = g.in(bb, nb); q.task = d_task;
+    q.B = B; q.W = W; q.hd = 1; q.E = E;
+    q.sWh = (long long)T_l * W; q.sbh = T_l; q.sh = (long long)B * W;
+    return q;
+  };
+  p.head = head(h, Wh, bh);
+  if (fused) p.thead = head(th, tWh, tbh);
+  p.mode = mode; p.fused_target = fused; p.clip = clip;
+  p.rew = g.in(rew, (size_t)B); p.done = g.in(done, (size_t)B); p.logpi = g.in(logpi, (size_t)B);
+  p.log_alpha = g.in(log_alpha, (size_t)T_glob); p.task = d_task; p.task_begin = task_begin;
+  p.y = g.in(y, (size_t)B); p.tw = g.in(tw, (size_t)B);
+  p.y_out = g.out<float>((size_t)B, "y_out");
+  p.dq = g.out<float>((size_t)E * B, "dq");
+  p.row_a = g.out<float>((size_t)B, "row_a");
+  p.row_b = g.out<float>((size_t)B, "row_b");
+  p.alpha_w = g.out<float>((size_t)B, "alpha_w");
+  p.dq_rec = rec_out(g, 0, "dq_rec");
+  p.gamma = gamma; p.use_task_weights = tw != nullptr; p.T_glob = T_glob; p.inv_norm = inv_norm;
+  int parts = -1;
+  p.dq_parts = &parts;
+  if (!g.ok) return -12;
+  critic_head(p, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("critic_head")) || (rc = g.check())) return rc;
+  *dq_parts = parts;
+  return g.back(y_out, p.y_out, (size_t)B) && g.back(dq, p.dq, (size_t)E * B) && g.back(row_a, p.row_a, (size_t)B) &&
+                 g.back(row_b, p.row_b, (size_t)B) && g.back(alpha_w, p.alpha_w, (size_t)B) &&
+                 g.back(dq_amax, p.dq_rec->amax, (size_t)PLANE_REC_PARTS)
+             ? 0
+             : -5;
+}
+
+int mtsac_debug_head_active_rows(int E, int B, const float* dq, int* n, int* rows, int* slot) {
+  if (E < 1 || E > 4 || B < 1 || !dq || !n || !rows || !slot) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  const float* d_dq = g.in(dq, (size_t)E * B);
+  int* d_n = g.out<int>((size_t)E, "n");
+  int* d_rows = g.out<int>((size_t)E * B, "rows");
+  int* d_slot = g.out<int>((size_t)E * B, "slot");
+  if (!g.ok) return -12;
+  active_rows(d_dq, E, B, d_n, d_rows, d_slot, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("active_rows")) || (rc = g.check())) return rc;
+  return g.back(n, d_n, (size_t)E) && g.back(rows, d_rows, (size_t)E * B) && g.back(slot, d_slot, (size_t)E * B) ? 0 : -5;
+}
+
+int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W, int hd, const int* task, const float* h,
+                              const float* Wh, const float* dout, const float* dq, float* dz, float* dbp, float* db,
+                              float* planes, float* dWh, float* dbh, int* counts, int* rows, int* info) {
+  const bool p3 = flags & 1, p2h = flags & 2, compact = form == 2;
+  const bool hd_ok = hd == 1 || hd == 2 || hd == 4 || hd == 6 || hd == 8;
+  if (form < 0 || form > 2 || (flags & ~3) || (p3 && p2h) || !hd_ok || E < 1 || E > 4 || W < 1 || !h || !Wh || !dout ||
+      !dz || !dbp || !db || !planes || !dWh || !dbh || !counts || !rows || !info || !tasks_ok(task, B, T_l) ||
+      (compact && (hd != 1 || W % 4 != 0 || !dq || !(p3 || p2h))) || (long long)E * B * W >= (1LL << 28))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const int chunks = head_backward_chunks(T_l);
+  const size_t nh = (size_t)E * B * W, nw = (size_t)E * T_l * W * hd, nd = (size_t)E * B * hd, np = p2h ? 2 : 3;
+  Guarded g;
+  TaskLists tl = make_lists(g, task, B, T_l);
+  HeadParams hp{};
+  hp.h = g.in(h, nh); hp.Wh = g.in(Wh, nw); hp.task = tl.d_task;
+  hp.B = B; hp.W = W; hp.hd = hd; hp.E = E;
+  hp.sWh = (long long)T_l * W * hd; hp.sbh = (long long)T_l * hd; hp.sh = (long long)B * W;
+  hp.fault = g.mem.get<unsigned>(1);  // zeroed
+  const float* d_dout = g.in(dout, nd);
+  float* d_dz = g.out<float>(nh, "dz");
+  float* d_dbp = g.out<float>((size_t)E * chunks * W, "dbp");
+  float* d_db = g.out<float>((size_t)E * W, "db");
+  float* d_dWh = g.out<float>(nw, "dWh");
+  float* d_dbh = g.out<float>((size_t)E * T_l * hd, "dbh");
+  PlaneOut po{};
+  std::vector<PlaneRec> hrec(2);
+  if (p3 || p2h) {
+    po.p = g.out<__bf16>(np * nh, "planes");
+    po.ld = W; po.ps = (long long)B * W; po.sm = (long long)np * po.ps;
+  }
+  if (p2h) {  // the bound's inputs: max |dout| as one partial maximum, max |head weight| in amax[1]
+    std::memset(hrec.data(), 0, sizeof(PlaneRec) * 2);
+    for (size_t i = 0; i < nd; ++i) hrec[0].amax[0] = std::max(hrec[0].amax[0], std::fabs(dout[i]));
+    for (size_t i = 0; i < nw; ++i) hrec[1].amax[1] = std::max(hrec[1].amax[1], std::fabs(Wh[i]));
+    const PlaneRec* r = g.in(hrec.data(), 2);
+    po.rc = rec_out(g, 0x7fffffff, "planes rec");
+    po.rd = r; po.nd = 1; po.rw = r + 1; po.w_add = 0.f; po.kmul = (float)hd;
+  }
+  int *d_n = nullptr, *d_slot = nullptr;
+  if (compact) {
+    const float* d_dq = g.in(dq, (size_t)E * B);
+    d_n = g.out<int>((size_t)E, "n");
+    int* d_ar = g.out<int>((size_t)E * B, "active rows");
+    d_slot = g.out<int>((size_t)E * B, "slot");
+    if (g.ok) active_rows(d_dq, E, B, d_n, d_ar, d_slot, nullptr);
+  }
+  if (!g.ok || !hp.fault) return -12;
+  std::fill(info, info + 8, 0);
+  const bool data = W % 4 == 0;  // the data pass's contract (kernels.h)
+  if (compact) {
+    head_backward_data(hp, d_dout, (long long)B * hd, nullptr, tl.counts, tl.rows, B, T_l, nullptr, po, nullptr, d_slot);
+  } else if (form == 1) {
+    info[0] = head_backward_both(hp, d_dout, (long long)B * hd, d_dz, tl.counts, tl.rows, B, T_l, po, d_dbp, d_dWh, d_dbh,
+                                 nullptr) ? 1 : 0;
+  } else {
+    if (data) head_backward_data(hp, d_dout, (long long)B * hd, d_dz, tl.counts, tl.rows, B, T_l, nullptr, po, d_dbp);
+    head_backward_weight(hp, d_dout, (long long)B * hd, tl.counts, tl.rows, B, d_dWh, d_dbh, nullptr);
+    info[0] = data ? 1 : 0;
+  }
+  if (!compact && info[0]) colsum_finish(d_dbp, W, chunks, E, d_db, W, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("head_backward")) || (rc = g.check())) return rc;
+  int ec = 0;
+  if (p2h && !g.back(&ec, &po.rc->e, 1)) return -5;
+  info[1] = ec;
+  unsigned fault = 0;
+  if (!g.back(&fault, hp.fault, 1)) return -5;
+  info[2] = (int)fault;
+  if (compact && !g.back(info + 3, d_n, (size_t)E)) return -5;
+  if (po.p) {
+    // a split2h launch that wrote no exponent leaves nothing to unscale: the planes come back as they lie (NaN)
+    for (int e = 0; e < E; ++e)
+      if (!planes_sum(po.p + (size_t)e * po.sm, np * (size_t)po.ps, (size_t)po.ps, (size_t)po.ps, p2h,
+                      ec == 0x7fffffff ? 0 : ec, planes + (size_t)e * po.ps))
+        return -5;
+  }
+  return g.back(dz, d_dz, nh) && g.back(dbp, d_dbp, (size_t)E * chunks * W) && g.back(db, d_db, (size_t)E * W) &&
+                 g.back(dWh, d_dWh, nw) && g.back(dbh, d_dbh, (size_t)E * T_l * hd) &&
+                 g.back(counts, tl.counts, (size_t)T_l) && g.back(rows, tl.rows, (size_t)T_l * B)
+             ? 0
+             : -5;
+}
+
+int mtsac_debug_head_action_grad(int B, int E, int Wc, int Ic, int A, const float* dz1, const float* dq, const float* W0,
+                                 const float* cache, const float* alpha_w, const float* a_data, int ld_a_data,
+                                 float explore_scale, float ls_min, float ls_max, const float* row_loss_in, float* dout,
+                                 float* row_loss, float* row_explore, float* dout_amax, int* dout_parts) {
+  if (B < 1 || E < 1 || E > 4 || Wc < 1 || A < 1 || A > 4 || Ic < A || !dz1 || !W0 || !cache || !alpha_w || !dout ||
+      !row_loss || !row_explore || !dout_amax || !dout_parts || (a_data && (ld_a_data < A || !row_loss_in)) ||
+      (long long)E * B * Wc >= (1LL << 28))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t nz = (size_t)E * B * Wc;
+  Guarded g;
+  ActionGradParams p{};
+  std::vector<float> zc;
+  if (dq) {  // member e's active rows (dq != 0) compacted in ascending order; the rest of the buffer is NaN
+    const float* d_dq = g.in(dq, (size_t)E * B);
+    int* d_n = g.out<int>((size_t)E, "n");
+    int* d_ar = g.out<int>((size_t)E * B, "active rows");
+    int* d_slot = g.out<int>((size_t)E * B, "slot");
+    if (!g.ok) return -12;
+    active_rows(d_dq, E, B, d_n, d_ar, d_slot, nullptr);
+    if (int rc = sync_rc("active_rows")) return rc;
+    std::vector<int> hs((size_t)E * B);
+    if (!g.back(hs.data(), d_slot, hs.size())) return -5;
+    zc.assign(nz, std::nanf(""));
+    for (size_t i = 0; i < hs.size(); ++i) {
+      if (hs[i] >= B) return -5;
+      if (hs[i] >= 0) std::copy(dz1 + i * Wc, dz1 + (i + 1) * Wc, zc.begin() + ((i / B) * B + hs[i]) * Wc);
+    }
+    p.slot = d_slot;
+  }
+  p.dz1 = g.in(dq ? zc.data() : dz1, nz);
+  p.W0 = g.in(W0, (size_t)E * Ic * Wc);
+  p.s_dz = (long long)B * Wc; p.s_W0 = (long long)Ic * Wc;
+  p.E = E; p.B = B; p.Wc = Wc; p.A = A;
+  p.cache = g.in(cache, (size_t)B * 5 * A);
+  p.alpha_w = g.in(alpha_w, (size_t)B);
+  p.ls_min = ls_min; p.ls_max = ls_max;
+  p.dout = g.out<float>((size_t)B * 2 * A, "dout");
+  p.dout_rec = rec_out(g, 0, "dout_rec");
+  int parts = -1;
+  p.dout_parts = &parts;
+  p.a_data = g.in(a_data, (size_t)B * (a_data ? ld_a_data : 0));
+  p.ld_a_data = ld_a_data; p.explore_scale = explore_scale;
+  p.row_loss = g.out<float>((size_t)B, "row_loss");
+  p.row_explore = g.out<float>((size_t)B, "row_explore");
+  if (!g.ok) return -12;
+  if (a_data && hipMemcpy(p.row_loss, row_loss_in, sizeof(float) * B, hipMemcpyHostToDevice) != hipSuccess) return -5;
+  action_grad(p, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("action_grad")) || (rc = g.check())) return rc;
+  *dout_parts = parts;
+  return g.back(dout, p.dout, (size_t)B * 2 * A) && g.back(row_loss, p.row_loss, (size_t)B) &&
+                 g.back(row_explore, p.row_explore, (size_t)B) && g.back(dout_amax, p.dout_rec->amax, (size_t)PLANE_REC_PARTS)
+             ? 0
+             : -5;
+}
+
+int mtsac_debug_head_row_alpha(int B, int T_l, int T_glob, int task_begin, int use_tw, const int* task,
+                               const float* log_alpha, float* alpha_row, float* tw_row) {
+  if (task_begin < 0 || T_glob < task_begin + T_l || !log_alpha || !alpha_row || !tw_row || !tasks_ok(task, B, T_l))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  const int* d_task = g.in(task, (size_t)B);
+  const float* d_la = g.in(log_alpha, (size_t)T_glob);
+  float* d_a = g.out<float>((size_t)B, "alpha_row");
+  float* d_tw = g.out<float>((size_t)B, "tw_row");
+  if (!g.ok) return -12;
+  row_alpha(d_task, task_begin, d_la, T_glob, B, use_tw != 0, d_a, d_tw, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("row_alpha")) || (rc = g.check())) return rc;
+  return g.back(alpha_row, d_a, (size_t)B) && g.back(tw_row, d_tw, (size_t)B) ? 0 : -5;
 }
 
 }  // extern "C"

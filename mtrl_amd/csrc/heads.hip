@@ -17,6 +17,9 @@
 
 namespace mtsac {
 
+int g_head_rw = -1;         // rows per wave of the grouped head kernels: -1 MTSAC_HEAD_RW / by grid size, 1 / 2 / 4 forced
+int g_head_bwd_split = -1;  // head_backward_both: -1 MTSAC_HEAD_BWD_SPLIT / by grid size, 0 the fused kernel, 1 both-in-one
+
 namespace {
 
 constexpr float LOG2F = 0.69314718055994530942f;
@@ -261,6 +264,7 @@ __global__ __launch_bounds__(256) void policy_head_pair_kernel(PolicyPair pp) {
 // S3, serialised: the policy-head pair 68.7 -> 39.8 us at 2 rows per wave instead of 4, the action
 // grad 43.5 -> 30.4 us at 1, profiles/r4t_*)
 static int rows_per_wave(long long wgs_at_rw1) {
+  if (g_head_rw == 1 || g_head_rw == 2 || g_head_rw == 4) return g_head_rw;  // mtsac_debug_head_rw (tests)
   static const int forced = [] {  // MTSAC_HEAD_RW=1 / 2 / 4: experiments
     const char* e = getenv("MTSAC_HEAD_RW");
     const int v = e ? atoi(e) : 0;
@@ -1216,7 +1220,8 @@ bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dou
   // the one-pass form has a workgroup per (task, 256 columns, member): below one per CU (task shards,
   // MT10) the separate passes' 5x more workgroups win (7-task shard: 27 / 18 us one-pass against
   // 15 / 11 us, profiles/r4u_sums_t7_split2h.txt vs r4g); bitwise the same either way
-  const bool split = split_req || (long long)T_l * gw * hp.E < 256;
+  const bool split = g_head_bwd_split >= 0 ? g_head_bwd_split != 0  // mtsac_debug_head_bwd_split (tests)
+                                            : split_req || (long long)T_l * gw * hp.E < 256;
   const dim3 grid((unsigned)(split ? gw * T_l * HB_RS * hp.E + T_l * gw * hp.E : T_l * gw * hp.E));
 #define HBB_LAUNCH(HDV)                                                                                         \
   if (split)                                                                                                    \

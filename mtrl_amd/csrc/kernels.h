@@ -391,6 +391,10 @@ void head_backward_data(const HeadParams& hp, const float* dout, long long s_dou
 // ascending b, slot[e * B + b] = s or -1 (a block scan per member: the same lists in every run)
 void active_rows(const float* dq, int E, int B, int* n, int* rows, int* slot, hipStream_t st);
 int head_backward_chunks(int T_l);
+// process-wide overrides of two launcher choices (tests: mtsac_debug_head_rw / mtsac_debug_head_bwd_split);
+// -1 (the default) leaves the environment's value and the automatic choice in force
+extern int g_head_rw;         // rows per wave of policy_head (grouped), policy_head_pair and action_grad: 1 / 2 / 4
+extern int g_head_bwd_split;  // head_backward_both: 0 the fused kernel, 1 the both-in-one-launch kernel
 // head_backward_data + head_backward_weight of one head in one launch (false: W % 4 != 0, not launched)
 bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
                         const int* rows, int max_rows, int T_l, PlaneOut po, float* dbp, float* dWh, float* dbh,

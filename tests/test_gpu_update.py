@@ -68,6 +68,11 @@ CONFIGS = {
     # headline widths (S2 with its clip=True, S3's 50 tasks) at a batch the float64 oracle runs in seconds
     "mt10_w2048_clip": dict(num_tasks=10, width=2048, n=16, clip=True),
     "mt50_w2048": dict(num_tasks=50, width=2048, n=4),
+    # the other action and ensemble sizes mtsac_create accepts: the padded critic input widths, the W0 action
+    # rows and the target entropy around the head kernels (tests/test_gpu_head_kernels.py has the kernels alone)
+    "a1_c1": dict(num_tasks=3, width=16, n=4, action_dim=1, num_critics=1),
+    "a3_c3": dict(num_tasks=3, width=16, n=4, action_dim=3, num_critics=3),
+    "a2_c4": dict(num_tasks=3, width=16, n=4, action_dim=2, num_critics=4),
 }
 
 
@@ -78,7 +83,9 @@ def test_update_matches_oracle(name, precision):
 
     spec = CONFIGS[name]
     T, W, n = spec["num_tasks"], spec["width"], spec["n"]
-    cfg = om.OracleConfig(num_tasks=T, obs_dim=39 + T, actor_width=W, critic_width=W,
+    A = spec.get("action_dim", 4)
+    cfg = om.OracleConfig(num_tasks=T, obs_dim=39 + T, actor_width=W, critic_width=W, action_dim=A,
+                          num_critics=spec.get("num_critics", 2),
                           actor_depth=spec.get("depth", 3), critic_depth=spec.get("depth", 3),
                           clip=spec.get("clip", False), use_task_weights=spec.get("use_task_weights", False))
     BATCH_PER_TASK[0] = n
@@ -87,8 +94,8 @@ def test_update_matches_oracle(name, precision):
     eng = _engine_for(cfg, precision=precision)
     _load_state(eng, st)
     for step in range(3):
-        batch = synthetic_batch(T, B, seed=100 + step, dtype=np.float32)
-        en, ec = synthetic_eps(B, seed=200 + step, dtype=np.float32)
+        batch = synthetic_batch(T, B, action_dim=A, seed=100 + step, dtype=np.float32)
+        en, ec = synthetic_eps(B, action_dim=A, seed=200 + step, dtype=np.float32)
         st, want = om.update(cfg, st, [b.astype(np.float64) for b in batch], en.astype(np.float64),
                              ec.astype(np.float64))
         eng.update(batch, en, ec)
