@@ -182,6 +182,46 @@ int mtsac_debug_head_action_grad(int B, int E, int Wc, int Ic, int A, const floa
 int mtsac_debug_head_row_alpha(int B, int T_l, int T_glob, int task_begin, int use_tw, const int* task,
                                const float* log_alpha, float* alpha_row, float* tw_row);
 
+/* The trunk GEMMs' bias-grad path and the layout kernels, one launch family at a time: device 0, null stream,
+ * host pointers in and out, outputs guarded as the head entries' are (an element left alone comes back NaN, or
+ * all-ones words; a written band returns -5 and names the buffer); -22 for bad sizes and -95 for a shape the
+ * kernel refuses, both before anything is launched.  Tests only.
+ *
+ * mtsac_debug_gemm_x3f with the engine's strides: epi bits 0-14 as there, bit 15 planes only (C may be null, the
+ * engine's data-grad form).  ld_n >= N (a multiple of 4) is the row stride of the output planes and of the mask
+ * planes (bit 8), rows_p >= M the rows allocated per plane (plane stride rows_p * ld_n; A's planes carry zero rows
+ * past M); C keeps ldc = N.  K is padded with zero columns to 64 (gemm_x3s, bit 9: to 32, so K = a padded width
+ * runs as the engine runs it; the caller's A then holds zeros in the columns past the width).  Csum
+ * [batch][rows_p][ld_n]: the sum of the written planes (precision bf16: the high plane), NaN wherever the kernel
+ * wrote nothing.  dbp: the column-sum partials as the launch leaves them, [batch][chunks][N] dense at the front of
+ * batch * gemm_x3f_max_row_tiles(M) * N floats (= ceil(M / 16) row tiles), the rest NaN; db [batch][N]:
+ * colsum_finish of dbp over the chunk count the engine derives for the next weight grad.  info [8]: 0 the family
+ * that ran (0 unsplit gemm_x3f, 1 split-K with the in-launch finish, 2 split-K with the finishing pass, 3
+ * gemm_x3s), 1 rows per dbp chunk as the engine computes them, 2 chunks = ceil(M / that), 3 K slices, 4 partial
+ * maxima the launcher reports, 5 gemm_x3f_max_row_tiles(M), 6 the split2h output exponent, 7 the launch's row
+ * tile (gemm_x3s: TI). */
+int mtsac_debug_gemm_x3f_ld(int epi, int batch, int M, int N, int K, int ld_n, int rows_p, const float* A,
+                            const float* B, float* C, const float* bias, const float* mask, float* Csum, float* dbp,
+                            float* db, int* info);
+/* The k-major x k-major gemm_x3p weight grad (split3) of E members with the bias grad finished from column-sum
+ * partials (SplitGemmParams::cs_part): A [E][K][M], B [E][K][N], part [E][chunks][N], splits (0: the launcher's
+ * choice) -> C [E][M][N] = A^T B, db [E][N].  mode 0 finishes at once (colsum_finish, or inside the split-K
+ * reduce launch); mode 1 defers the finish to a FinishSink that holds a colsum_job on part_pre [E][nb[0]][nb[1]]
+ * before it and one on part_post [E][nb[2]][nb[3]] after it, all run by one finish_many: db_pre [E][nb[1]],
+ * db_post [E][nb[3]] come back too (mode 0 ignores nb and the four).  info [4]: 0 K slices used, 1 who finished
+ * the bias grad (0 colsum_finish, 1 the reduce launch, 2 finish_many), 2 the sink's jobs, 3 slab-sum blocks of
+ * the deferred job. */
+int mtsac_debug_wgrad_finish(int mode, int E, int M, int N, int K, int chunks, int splits, const float* A,
+                             const float* B, const float* part, const int* nb, const float* part_pre,
+                             const float* part_post, float* C, float* db, float* db_pre, float* db_post, int* info);
+/* The layout kernels.  kind 0 split_planes: dims [12] = rows, cols, ldx, out_rows, out_cols, ldo, rows allocated
+ * per plane (plane stride = that * ldo), transpose, batch, frag, split2h, its exponent; x [batch][rows][ldx];
+ * out: the raw 16-bit plane words [batch][3][allocated rows][ldo].  kind 1 transpose_f32: dims = rows, cols,
+ * batch; out [batch][cols][rows].  kind 2 colsum: dims = rows, cols, ld, batch; x [batch][rows][ld]; out: part
+ * [batch][chunks][cols] dense at the front of batch * 64 * cols floats (chunks = min(64, ceil(rows / 256)), the
+ * rest NaN), out2: db [batch][cols]. */
+int mtsac_debug_layout(int kind, const int* dims, const float* x, void* out, void* out2);
+
 /* Eager update_many overlaps consecutive steps (the next gather and critic(s, a) forward beside
  * the previous actor backward / all-reduce / Adam): on = 1 always, 0 never (whole steps), -1 the
  * default (when the trunk gradients go through a device collective: RCCL or the modelled one).

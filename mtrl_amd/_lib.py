@@ -191,6 +191,9 @@ SIGNATURES = {
     "mtsac_debug_head_action_grad": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 6 + [ctypes.c_int] +
                                      [ctypes.c_float] * 3 + [P] * 6),
     "mtsac_debug_head_row_alpha": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 4),
+    "mtsac_debug_gemm_x3f_ld": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 9),
+    "mtsac_debug_wgrad_finish": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 11),
+    "mtsac_debug_layout": (ctypes.c_int, [ctypes.c_int] + [P] * 4),
     "mtsac_debug_set_pipeline": (ctypes.c_int, [P, I32]),
     "mtsac_debug_lane_mode": (ctypes.c_int, [P]),
     "mtsac_debug_opt_form": (ctypes.c_int, [P, ctypes.c_int]),

@@ -195,6 +195,20 @@ bool planes_sum(const __bf16* dev, size_t n_words, size_t ps, size_t n, bool h2,
   return true;
 }
 
+// split2h test records: max |x| and the plane exponent of that bound, as plane_exp (gemm_common.h) gives it
+float host_amax(const float* x, size_t n) {
+  float m = 0.f;
+  for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(x[i]));
+  return m;
+}
+int host_plane_exp(float b) {
+  b *= 1.00390625f;
+  if (!(b > 0.f)) return 0;
+  int ex;
+  (void)std::frexp(b, &ex);
+  return 15 - ex;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1176,6 +1190,278 @@ int mtsac_debug_head_row_alpha(int B, int T_l, int T_glob, int task_begin, int u
   int rc = 0;
   if ((rc = sync_rc("row_alpha")) || (rc = g.check())) return rc;
   return g.back(alpha_row, d_a, (size_t)B) && g.back(tw_row, d_tw, (size_t)B) ? 0 : -5;
+}
+
+// gemm_x3f / gemm_x3s as the engine's trunk calls them (mtsac_debug.h): padded plane strides, guarded
+// outputs, the bias grad's column-sum partials and their finish over the engine's own chunk count
+int mtsac_debug_gemm_x3f_ld(int epi, int batch, int M, int N, int K, int ld_n, int rows_p, const float* A,
+                            const float* B, float* C, const float* bias, const float* mask, float* Csum, float* dbp,
+                            float* db, int* info) {
+  const bool m16 = (epi >> 8) & 1;
+  const bool small = (epi >> 9) & 1;          // gemm_x3s instead
+  const int np = ((epi >> 10) & 1) ? 1 : 3;   // bf16: the high plane only
+  const bool autosplit = (epi >> 11) & 1;     // split-K by the launcher's own choice (workspace given)
+  const bool fin = (epi >> 12) & 1;           // ... with arrival counters: the in-launch finish
+  const bool h2 = (epi >> 13) & 1;            // precision split2h
+  const bool bfrag = (epi >> 14) & 1;         // B planes in the fragment layout (N % 16 == 0)
+  const bool ponly = (epi >> 15) & 1;         // planes only: the engine's data-grad form
+  epi &= 255;
+  if (M < 1 || N < 1 || K < 1 || batch < 1 || batch > 8 || ld_n < N || ld_n % 4 != 0 || rows_p < M || !A || !B ||
+      !Csum || !dbp || !db || !info || (!ponly && !C) || (epi != EPI_BIAS_RELU && epi != EPI_RELU_MASK) ||
+      (epi == EPI_BIAS_RELU && !bias) || (epi == EPI_RELU_MASK && !mask) || (bfrag && N % 16 != 0) ||
+      (h2 && np == 1) || (long long)batch * rows_p * ld_n >= (1LL << 28))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const long long Kp = small ? up32(K) : (K + 63) / 64 * 64;  // gemm_x3s steps K by 32 (the engine's padded width)
+  const size_t nA = (size_t)M * K * batch, nB = (size_t)N * K * batch, nC = (size_t)M * N * batch;
+  const long long pp = (long long)rows_p * ld_n;  // plane stride of the output and mask planes
+  const int maxrt = gemm_x3f_max_row_tiles(M);
+  Guarded gd;
+  std::vector<PlaneRec> hrec(4);
+  std::memset(hrec.data(), 0, sizeof(PlaneRec) * 4);
+  if (h2) {  // records of A, B (its max covering the bias, as a trunk record does), the mask and C
+    const float ma = host_amax(A, nA), mbias = epi == EPI_BIAS_RELU ? host_amax(bias, (size_t)N * batch) : 0.f;
+    const float mb = std::max(host_amax(B, nB), mbias), mm = mask ? host_amax(mask, nC) : 1.f;
+    hrec[0].e = host_plane_exp(ma); hrec[0].amax[0] = ma;
+    hrec[1].e = host_plane_exp(mb); hrec[1].amax[0] = mb;
+    hrec[2].e = host_plane_exp(mm); hrec[2].amax[0] = mm;
+  }
+  PlaneRec* rec = gd.in(hrec.data(), 4);
+  const float *dA = gd.in(A, nA), *dB = gd.in(B, nB), *dbias = gd.in(bias, (size_t)N * batch), *dmask = gd.in(mask, nC);
+  __bf16* Ap = gd.mem.get<__bf16>((size_t)3 * rows_p * Kp * batch);
+  __bf16* Bp = gd.mem.get<__bf16>((size_t)3 * N * Kp * batch);
+  __bf16* Mp = m16 ? gd.mem.get<__bf16>((size_t)3 * pp * batch) : nullptr;
+  float* dC = ponly ? nullptr : gd.out<float>(nC, "C");
+  __bf16* dCp = gd.out<__bf16>((size_t)3 * pp * batch, "C planes");
+  float* d_dbp = gd.out<float>((size_t)batch * maxrt * N, "dbp");
+  float* d_db = gd.out<float>((size_t)batch * N, "db");
+  if (!gd.ok || !rec || !Ap || !Bp || (m16 && !Mp)) return -12;
+  SplitGemmParams g{};
+  g.A = Ap; g.lda = Kp; g.pA = (long long)rows_p * Kp; g.sA = 3 * g.pA;
+  g.B = Bp; g.ldb = Kp; g.pB = (long long)N * Kp; g.sB = 3 * g.pB;
+  g.b_frag = bfrag ? 1 : 0;
+  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
+  g.bias = dbias; g.sBias = N;
+  if (m16) {
+    g.mask16 = Mp; g.ldm = ld_n; g.sMask = 3 * pp;
+  } else {
+    g.mask = dmask; g.ldm = N; g.sMask = (long long)M * N;
+  }
+  g.pMask = pp;
+  g.Cp = dCp; g.ldcp = ld_n; g.pC = pp; g.sCp = 3 * pp;
+  g.M = M; g.N = N; g.K = (int)Kp;
+  g.np = h2 ? 2 : np;
+  g.dbp = d_dbp;
+  int nparts = 0;
+  g.nparts = &nparts;
+  if (h2) {
+    g.ra = rec + 0; g.na = 1;
+    g.rb = rec + 1; g.nb = 1;
+    g.rc = rec + 3;
+    g.bias_in_b = epi == EPI_BIAS_RELU ? 1 : 0;
+    g.kmul = (float)K;
+  }
+  if (autosplit) {
+    g.ws = gd.mem.get<float>((size_t)std::max(gemm_x3f_ws_floats(M, N, (int)Kp, batch), 1LL));
+    if (!g.ws) return -12;
+    g.splits = -1;
+    if (fin && !(g.cnt = gd.mem.get<int>((size_t)GEMM_X3F_CNT))) return -12;  // zeroed
+  }
+  if (small ? !gemm_x3s_ok(g, epi, batch) : !gemm_x3f_ok(g, epi, batch)) return -95;
+  // rows per column-sum chunk and the chunk count, by the rule the engine's dgrad_params uses
+  const int bm = dbp_chunk_rows(g, epi, batch, !small);
+  const int chunks = (M + bm - 1) / bm;
+  if (chunks > maxrt) return -95;
+  for (int z = 0; z < batch; ++z) {
+    SplitParams s{};
+    s.x = dA + (size_t)z * M * K; s.ldx = K; s.rows = M; s.cols = K;
+    s.out = Ap + (size_t)z * 3 * rows_p * Kp; s.ldo = Kp; s.po = (long long)rows_p * Kp; s.out_rows = rows_p;
+    s.out_cols = (int)Kp;
+    s.e2h = h2 ? &rec[0].e : nullptr;
+    split_planes(s, false, 1, nullptr);  // zero rows past M, zero columns past K
+    s.x = dB + (size_t)z * N * K; s.rows = N;
+    s.out = Bp + (size_t)z * 3 * N * Kp; s.po = (long long)N * Kp; s.out_rows = N;
+    s.e2h = h2 ? &rec[1].e : nullptr;
+    s.frag = bfrag ? 1 : 0;
+    split_planes(s, false, 1, nullptr);
+    s.frag = 0;
+    if (m16) {  // planes of the mask, row stride ld_n, rows_p rows per plane (zeros in the padding)
+      s.x = dmask + (size_t)z * M * N; s.ldx = N; s.rows = M; s.cols = N;
+      s.out = Mp + (size_t)z * 3 * pp; s.ldo = ld_n; s.po = pp; s.out_rows = rows_p; s.out_cols = ld_n;
+      s.e2h = h2 ? &rec[2].e : nullptr;
+      split_planes(s, false, 1, nullptr);
+    }
+  }
+  int rc = 0;
+  if ((rc = sync_rc("split_planes"))) return rc;
+  int slices = 1;
+  if (small) gemm_x3s(g, epi, batch, nullptr);
+  else slices = gemm_x3f(g, epi, batch, nullptr);
+  colsum_finish(d_dbp, N, chunks, batch, d_db, N, nullptr);
+  if ((rc = sync_rc(small ? "gemm_x3s" : "gemm_x3f")) || (rc = gd.check())) return rc;
+  int ec = 0;
+  if (h2 && !gd.back(&ec, &rec[3].e, 1)) return -5;
+  // split launches: the in-launch finish keeps the split row tile, the finishing pass sums shorter chunks
+  info[0] = small ? 3 : slices <= 1 ? 0 : bm == gemm_x3f_split_bm(M, N, (int)Kp, batch) ? 1 : 2;
+  info[1] = bm;
+  info[2] = chunks;
+  info[3] = slices;
+  info[4] = nparts;
+  info[5] = maxrt;
+  info[6] = ec;
+  info[7] = small ? gemm_x3s_ti(M, N, batch) : slices > 1 ? gemm_x3f_split_bm(M, N, (int)Kp, batch) : gemm_x3f_bm(g, batch);
+  if (dC && !gd.back(C, dC, nC)) return -5;
+  // bf16 keeps the high plane only (gemm_x3f leaves the other two alone)
+  const size_t per = (size_t)pp;
+  for (int z = 0; z < batch; ++z) {
+    if (np == 1 && !h2) {
+      std::vector<__bf16> h(per);
+      if (hipMemcpy(h.data(), dCp + (size_t)z * 3 * per, per * 2, hipMemcpyDeviceToHost) != hipSuccess) return -5;
+      for (size_t i = 0; i < per; ++i) Csum[(size_t)z * per + i] = (float)h[i];
+    } else if (!planes_sum(dCp + (size_t)z * 3 * per, 3 * per, per, per, h2, ec, Csum + (size_t)z * per)) {
+      return -5;
+    }
+  }
+  return gd.back(dbp, d_dbp, (size_t)batch * maxrt * N) && gd.back(db, d_db, (size_t)batch * N) ? 0 : -5;
+}
+
+// the k-major x k-major gemm_x3p weight grad with the bias grad finished from column-sum partials
+// (mtsac_debug.h): at once, or through a FinishSink between two unrelated colsum jobs
+int mtsac_debug_wgrad_finish(int mode, int E, int M, int N, int K, int chunks, int splits, const float* A,
+                             const float* B, const float* part, const int* nb, const float* part_pre,
+                             const float* part_post, float* C, float* db, float* db_pre, float* db_post, int* info) {
+  if (mode < 0 || mode > 1 || E < 1 || E > 8 || M < 1 || N < 1 || K < 1 || chunks < 1 || splits < 0 || splits > 64 ||
+      !A || !B || !part || !C || !db || !info || (long long)E * K * std::max(M, N) >= (1LL << 28))
+    return -22;
+  if (mode == 1 && (!nb || !part_pre || !part_post || !db_pre || !db_post || nb[0] < 1 || nb[1] < 1 || nb[2] < 1 ||
+                    nb[3] < 1))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const int Kp = (int)up32(K);
+  long long lda, pa, ldb, pb;
+  plane_geom(M, K, true, lda, pa);
+  plane_geom(N, K, true, ldb, pb);
+  Guarded gd;
+  const float *dA = gd.in(A, (size_t)E * K * M), *dB = gd.in(B, (size_t)E * K * N);
+  const float* dpart = gd.in(part, (size_t)E * chunks * N);
+  __bf16* Ap = gd.mem.get<__bf16>((size_t)3 * pa * E);
+  __bf16* Bp = gd.mem.get<__bf16>((size_t)3 * pb * E);
+  float* dC = gd.out<float>((size_t)E * M * N, "C");
+  float* d_db = gd.out<float>((size_t)E * N, "db");
+  const int want = splits == 0 ? gemm_x3p_splits(M, N, Kp, E, true, 3) : splits;
+  float* ws = gd.mem.get<float>((size_t)std::max(gemm_ws_floats(M, N, E, std::max(want, 2)), 1LL));
+  if (!gd.ok || !Ap || !Bp || !ws) return -12;
+  const float *dpre = nullptr, *dpost = nullptr;
+  float *d_dbpre = nullptr, *d_dbpost = nullptr;
+  if (mode == 1) {
+    dpre = gd.in(part_pre, (size_t)E * nb[0] * nb[1]);
+    dpost = gd.in(part_post, (size_t)E * nb[2] * nb[3]);
+    d_dbpre = gd.out<float>((size_t)E * nb[1], "db_pre");
+    d_dbpost = gd.out<float>((size_t)E * nb[3], "db_post");
+    if (!gd.ok) return -12;
+  }
+  for (int z = 0; z < E; ++z) {
+    split_into(dA + (size_t)z * K * M, M, K, true, Ap + 3 * pa * z);
+    split_into(dB + (size_t)z * K * N, N, K, true, Bp + 3 * pb * z);
+  }
+  SplitGemmParams g{};
+  g.A = Ap; g.lda = lda; g.pA = pa; g.sA = 3 * pa; g.a_kmajor = 1;
+  g.B = Bp; g.ldb = ldb; g.pB = pb; g.sB = 3 * pb; g.b_kmajor = 1;
+  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
+  g.M = M; g.N = N; g.K = Kp;
+  g.splits = splits == 0 ? -1 : splits;
+  g.ws = ws;
+  g.cs_part = dpart; g.cs_chunks = chunks; g.cs_db = d_db; g.cs_sdb = N;
+  // the slices gemm_x3p makes of that request (whole 32-deep K tiles per slice)
+  int S = 1;
+  if (want > 1) {
+    const int kchunk = (Kp / 32 + want - 1) / want * 32;
+    S = (Kp + kchunk - 1) / kchunk;
+  }
+  FinishSink sink;
+  int this_job = -1;
+  if (mode == 1) {
+    sink.job[sink.n++] = colsum_job(dpre, nb[1], nb[0], d_dbpre, nb[1]);
+    g.defer = &sink;
+    this_job = sink.n;
+  }
+  gemm_x3p(g, EPI_STORE, E, nullptr);
+  info[0] = S;
+  info[1] = mode == 1 ? 2 : S > 1 ? 1 : 0;  // who finishes the bias grad: colsum_finish, the reduce launch, finish_many
+  info[2] = mode == 1 ? sink.n : 0;
+  info[3] = mode == 1 && sink.n > this_job ? sink.job[this_job].nred : 0;
+  if (mode == 1) {
+    if (sink.n != this_job + 1) return -5;  // the launcher did not defer its finish
+    sink.job[sink.n++] = colsum_job(dpost, nb[3], nb[2], d_dbpost, nb[3]);
+    info[2] = sink.n;
+    finish_many(sink, E, nullptr);
+  }
+  int rc = 0;
+  if ((rc = sync_rc("wgrad finish")) || (rc = gd.check())) return rc;
+  if (mode == 1 && (!gd.back(db_pre, d_dbpre, (size_t)E * nb[1]) || !gd.back(db_post, d_dbpost, (size_t)E * nb[3])))
+    return -5;
+  return gd.back(C, dC, (size_t)E * M * N) && gd.back(db, d_db, (size_t)E * N) ? 0 : -5;
+}
+
+// the layout kernels alone (mtsac_debug.h): split_planes, transpose_f32, colsum
+int mtsac_debug_layout(int kind, const int* dims, const float* x, void* out, void* out2) {
+  if (kind < 0 || kind > 2 || !dims || !x || !out) return -22;
+  if (kind == 0) {
+    const int rows = dims[0], cols = dims[1], ldx = dims[2], out_rows = dims[3], out_cols = dims[4], ldo = dims[5],
+              arows = dims[6], tr = dims[7], batch = dims[8], frag = dims[9], h2 = dims[10], e = dims[11];
+    if (rows < 1 || cols < 1 || ldx < cols || out_rows < 1 || out_cols < 1 || ldo < out_cols || arows < out_rows ||
+        (tr & ~1) || batch < 1 || batch > 8 || (frag & ~1) || (h2 & ~1) || e < -100 || e > 100 ||
+        (frag && (ldo % 32 != 0 || arows % 16 != 0)) || (long long)batch * arows * ldo >= (1LL << 27) ||
+        (long long)batch * rows * ldx >= (1LL << 27))
+      return -22;
+    if (hipSetDevice(0) != hipSuccess) return -5;
+    Guarded gd;
+    const long long po = (long long)arows * ldo;
+    const float* dx = gd.in(x, (size_t)batch * rows * ldx);
+    const int* de = gd.in(&e, 1);
+    __bf16* dout = gd.out<__bf16>((size_t)batch * 3 * po, "planes");
+    if (!gd.ok) return -12;
+    SplitParams s{};
+    s.x = dx; s.ldx = ldx; s.sx = (long long)rows * ldx; s.rows = rows; s.cols = cols;
+    s.out = dout; s.ldo = ldo; s.po = po; s.so = 3 * po; s.out_rows = out_rows; s.out_cols = out_cols;
+    s.e2h = h2 ? de : nullptr;
+    s.frag = frag;
+    split_planes(s, tr != 0, batch, nullptr);
+    int rc = 0;
+    if ((rc = sync_rc("split_planes")) || (rc = gd.check())) return rc;
+    return gd.back(reinterpret_cast<__bf16*>(out), dout, (size_t)batch * 3 * po) ? 0 : -5;
+  }
+  if (kind == 1) {
+    const int rows = dims[0], cols = dims[1], batch = dims[2];
+    if (rows < 1 || cols < 1 || batch < 1 || batch > 8 || (long long)batch * rows * cols >= (1LL << 27)) return -22;
+    if (hipSetDevice(0) != hipSuccess) return -5;
+    Guarded gd;
+    const size_t n = (size_t)rows * cols;
+    const float* dx = gd.in(x, n * batch);
+    float* dout = gd.out<float>(n * batch, "transposed");
+    if (!gd.ok) return -12;
+    transpose_f32(dx, (long long)n, dout, (long long)n, rows, cols, batch, nullptr);
+    int rc = 0;
+    if ((rc = sync_rc("transpose_f32")) || (rc = gd.check())) return rc;
+    return gd.back(reinterpret_cast<float*>(out), dout, n * batch) ? 0 : -5;
+  }
+  const int rows = dims[0], cols = dims[1], ld = dims[2], batch = dims[3];
+  if (rows < 1 || cols < 1 || ld < cols || batch < 1 || batch > 8 || !out2 ||
+      (long long)batch * rows * ld >= (1LL << 27))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded gd;
+  const float* dx = gd.in(x, (size_t)batch * rows * ld);
+  float* dpart = gd.out<float>((size_t)batch * COLSUM_CHUNKS * cols, "part");
+  float* d_db = gd.out<float>((size_t)batch * cols, "db");
+  if (!gd.ok) return -12;
+  colsum(dx, rows, cols, ld, (long long)rows * ld, batch, dpart, d_db, cols, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("colsum")) || (rc = gd.check())) return rc;
+  return gd.back(reinterpret_cast<float*>(out), dpart, (size_t)batch * COLSUM_CHUNKS * cols) &&
+                 gd.back(reinterpret_cast<float*>(out2), d_db, (size_t)batch * cols)
+             ? 0
+             : -5;
 }
 
 }  // extern "C"

@@ -830,7 +830,7 @@ struct mtsac_engine {
       const bool fx = gemm_x3f_ok(q, EPI_RELU_MASK, net.E);
       const bool fs = !fx && !gemm_x3f_ok(g, EPI_RELU_MASK, net.E) && gemm_x3s_ok(q, EPI_RELU_MASK, net.E);
       if (fx || fs) g = q;
-      const int bm = fx ? gemm_x3f_out_bm(q, EPI_RELU_MASK, net.E) : 16 * gemm_x3s_ti(M, net.width, net.E);
+      const int bm = dbp_chunk_rows(q, EPI_RELU_MASK, net.E, fx);
       if (db_chunks) *db_chunks = (fx || fs) ? (M + bm - 1) / bm : 0;
     }
     return g;

@@ -195,6 +195,12 @@ bool gemm_x3s_ok(const SplitGemmParams& p, int epi, int batch);
 void gemm_x3s(const SplitGemmParams& p, int epi, int batch, hipStream_t st);
 int gemm_x3s_ti(int M, int N, int batch);
 void gemm_x3s_ablate(const SplitGemmParams& p, int abl, int batch, hipStream_t st);  // experiments
+// rows per chunk of the column-sum partials (p.dbp) the launch leaves: its row tile (x3f: gemm_x3f runs it,
+// else gemm_x3s); the next weight grad finishes ceil(M / that) chunks.  One rule for the engine and the
+// single-kernel test entry.
+inline int dbp_chunk_rows(const SplitGemmParams& p, int epi, int batch, bool x3f) {
+  return x3f ? gemm_x3f_out_bm(p, epi, batch) : 16 * gemm_x3s_ti(p.M, p.N, batch);
+}
 extern int g_x3p_geo;  // tile geometry of gemm_x3p (-1: by operand form, 0..3: forced; see gemm_x3p.hip)
 extern int g_x3p_dbg;  // experiment bits OR-ed into SplitGemmParams::dbg
 extern int g_x3_dbg;   // experiments on gemm_x3: bit0 skip loads after the first tile, bit1 skip MFMA, bit2 skip split

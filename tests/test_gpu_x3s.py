@@ -1,9 +1,10 @@
 """gemm_x3s (mtrl_amd/csrc/gemm_x3s.hip): the small-row-count plane GEMM of the trunk forward and
 data grad (task shards, MT10), 16 TI x 64 tiles with the K range split over the 4 waves of a
 workgroup.  Checked against float64 numpy with the fp32-GEMM bound |err| <= 4e-6 sum|a b|, on the
-shapes a rank of the 8-way MT50 job and MT10 run (B = 768 / 896 / 1280, W = 2048 and 400), every
-tile height (TI = 4..8), ragged edges (rows past M, a partial column tile, odd K-step counts: the
-phantom step) and every epilogue."""
+shapes a rank of the 8-way MT50 job and MT10 run (B = 768 / 896 / 1280, W = 2048 and 400), the tile
+heights these shapes get (TI = 5 and 7; 4 and 6, split2h and the engine's padded strides are in
+test_gpu_trunk_bias.py; TI = 8 is never picked, see test_tile_heights), ragged edges (rows past M, a
+partial column tile, odd K-step counts: the phantom step) and every epilogue."""
 
 from __future__ import annotations
 
@@ -79,12 +80,21 @@ def test_fp32_only_output():
 
 
 def test_tile_heights():
-    """gemm_x3s_ti: every tile height the cost model picks is exercised above."""
+    """gemm_x3s_ti: the shapes above run TI = 5 and 7 (TI = 4 and 6 run in test_gpu_trunk_bias.py).  TI = 8 is
+    never picked: a 64-row tile needs at most twice the 128-row tile's workgroups, so at most twice its rounds,
+    its cost is never larger and ties go to the smaller tile.  The launcher agrees with the rule restated in
+    trunk_bias_ref over a sweep of shapes."""
+    import trunk_bias_ref as R
     from mtrl_amd import _lib as L
 
     lib = L.load()
     got = {lib.mtsac_debug_x3s_ti(M, N, E) for E, M, N, _ in SHAPES}
     assert got >= {5, 7}, got
+    sweep = [(M, N, E) for M in list(range(1, 700, 13)) + [896, 1280, 3200, 6400, 100000] for N in (8, 400, 2048)
+             for E in (1, 2)]
+    picked = {s: lib.mtsac_debug_x3s_ti(*s) for s in sweep}
+    assert all(picked[s] == R.x3s_ti(*s) for s in sweep)
+    assert set(picked.values()) == {4, 5, 6, 7}, set(picked.values())
 
 
 def test_fp32_mask_rejected():
