@@ -43,23 +43,23 @@ class MTSACConfig(AlgorithmConfig):
     n_atoms: int = 51
 
 
+# the engine's gradient-surgery modes (MTSAC.surgery): the fields of the optimizer's state that the reference logs
+_SURGERY_LOG_KEYS = {"pcgrad": PCGRAD_LOG_KEYS, "cagrad": CAGRAD_LOG_KEYS, "gradnorm": GRADNORM_LOG_KEYS}
+
+
 class _DeviceLogs(Mapping):
     """The update's LogDict, fetched from the device on first access (like jax.device_get)."""
 
-    def __init__(self, engine: MTSACEngine, pcgrad: bool = False, cagrad: bool = False, gradnorm: bool = False):
-        self._engine, self._d, self._pcgrad, self._cagrad, self._gradnorm = engine, None, pcgrad, cagrad, gradnorm
+    def __init__(self, engine: MTSACEngine, surgery: str | None = None):
+        self._engine, self._d, self._surgery = engine, None, surgery
 
     def _get(self):
         if self._d is None:
             self._d = self._engine.logs()
-            if self._pcgrad:  # the PCGradState of both optimizers (mtrl/optim/pcgrad.py:12-17)
-                self._d.update(self._engine.pcgrad_logs())
-            if self._cagrad:  # the CAGradState of both optimizers (mtrl/optim/cagrad.py:12-17)
-                self._d.update(self._engine.cagrad_logs())
-            if self._gradnorm:  # the GradNormState arrays of both optimizers (mtrl/optim/gradnorm.py:34-37)
-                g = self._engine.gradnorm_logs()
+            if self._surgery:  # the PCGradState / CAGradState / GradNormState fields of both optimizers
+                g = getattr(self._engine, f"{self._surgery}_logs")()
                 self._d.update({f"metrics/{net}_{k}": g[f"metrics/{net}_{k}"] for net in ("critic", "actor")
-                                for k in GRADNORM_LOG_KEYS})
+                                for k in _SURGERY_LOG_KEYS[self._surgery]})
         return self._d
 
     def __getitem__(self, k):
@@ -69,9 +69,7 @@ class _DeviceLogs(Mapping):
         return iter(self._get())
 
     def __len__(self):
-        return (len(L.LOG_KEYS) + (2 * len(PCGRAD_LOG_KEYS) if self._pcgrad else 0) +
-                (2 * len(CAGRAD_LOG_KEYS) if self._cagrad else 0) +
-                (2 * len(GRADNORM_LOG_KEYS) if self._gradnorm else 0))
+        return len(L.LOG_KEYS) + 2 * len(_SURGERY_LOG_KEYS.get(self._surgery, ()))
 
 
 def _check_supported(net, what: str):
@@ -88,80 +86,38 @@ def _check_supported(net, what: str):
             f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad, CAGrad or GradNorm")
 
 
-def _check_pcgrad(config: "MTSACConfig", task_shard) -> bool:
-    """True when both optimizers are PCGrad; raises for what the engine's PCGrad step does not run."""
+def _check_surgery(config: "MTSACConfig", task_shard, config_cls, name: str, one_network: str, sharded: str,
+                   tail=None) -> bool:
+    """True when both optimizers are ``config_cls``; raises for what the engine's step of that method does not
+    run.  ``one_network``, ``sharded``: the method's own reason why the reference / the engine cannot;
+    ``tail(opt_a, opt_c)``: its own further checks."""
     opt_a = config.actor_config.network_config.optimizer
     opt_c = config.critic_config.network_config.optimizer
-    pa, pc = isinstance(opt_a, PCGradConfig), isinstance(opt_c, PCGradConfig)
-    if not (pa or pc):
+    on_a, on_c = isinstance(opt_a, config_cls), isinstance(opt_c, config_cls)
+    if not (on_a or on_c):
         return False
-    if pa != pc:
+    if on_a != on_c:
         raise NotImplementedError(
-            "PCGrad on one network only: the reference itself cannot run it (mtsac.py:581 averages the critic's "
-            "per-task gradients unless the ACTOR's optimizer is PCGrad, and pcgrad's shape assert then fails); "
-            "give both actor and critic a PCGradConfig")
+            f"{name} on one network only: {one_network}; give both actor and critic a {config_cls.__name__}")
     if opt_a.num_tasks != config.num_tasks or opt_c.num_tasks != config.num_tasks:
-        raise ValueError("PCGradConfig.num_tasks must equal the algorithm's num_tasks")
+        raise ValueError(f"{config_cls.__name__}.num_tasks must equal the algorithm's num_tasks")
+    if config.use_task_weights:
+        raise NotImplementedError(
+            f"{name} with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
+            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
+    if task_shard is not None:
+        raise NotImplementedError(f"{name} on a task-sharded engine: {sharded}")
+    if tail:
+        tail(opt_a, opt_c)
+    return True
+
+
+def _pcgrad_tail(opt_a, opt_c) -> None:
     if opt_a.cosine_sim_logs != opt_c.cosine_sim_logs:
         raise NotImplementedError("PCGrad: cosine_sim_logs must agree between actor and critic (one engine switch)")
-    if config.use_task_weights:
-        raise NotImplementedError(
-            "PCGrad with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
-            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
-    if task_shard is not None:
-        raise NotImplementedError(
-            "PCGrad on a task-sharded engine: the surgery needs every task's gradient of the whole network on "
-            "one engine (the Gram matrix couples all tasks)")
-    return True
 
 
-def _check_cagrad(config: "MTSACConfig", task_shard) -> bool:
-    """True when both optimizers are CAGrad; raises for what the engine's CAGrad step does not run."""
-    opt_a = config.actor_config.network_config.optimizer
-    opt_c = config.critic_config.network_config.optimizer
-    ca, cc = isinstance(opt_a, CAGradConfig), isinstance(opt_c, CAGradConfig)
-    if not (ca or cc):
-        return False
-    if ca != cc:
-        raise NotImplementedError(
-            "CAGrad on one network only: the reference hands the critic's optimizer per-task gradients only when "
-            "the ACTOR's optimizer asks for split losses (mtsac.py:581), and cagrad's shape assert fails on "
-            "anything else; give both actor and critic a CAGradConfig")
-    if opt_a.num_tasks != config.num_tasks or opt_c.num_tasks != config.num_tasks:
-        raise ValueError("CAGradConfig.num_tasks must equal the algorithm's num_tasks")
-    if config.use_task_weights:
-        raise NotImplementedError(
-            "CAGrad with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
-            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
-    if task_shard is not None:
-        raise NotImplementedError(
-            "CAGrad on a task-sharded engine: the weight search needs every task's gradient of the whole network "
-            "on one engine (the Gram matrix couples all tasks)")
-    return True
-
-
-def _check_gradnorm(config: "MTSACConfig", task_shard) -> bool:
-    """True when both optimizers are GradNorm; raises for what the engine's GradNorm step does not run."""
-    opt_a = config.actor_config.network_config.optimizer
-    opt_c = config.critic_config.network_config.optimizer
-    ga, gc = isinstance(opt_a, GradNormConfig), isinstance(opt_c, GradNormConfig)
-    if not (ga or gc):
-        return False
-    if ga != gc:
-        raise NotImplementedError(
-            "GradNorm on one network only: the reference hands the critic's optimizer per-task gradients only "
-            "when the ACTOR's optimizer asks for split losses (mtsac.py:581), and gradnorm's shape assert fails "
-            "on anything else; give both actor and critic a GradNormConfig")
-    if opt_a.num_tasks != config.num_tasks or opt_c.num_tasks != config.num_tasks:
-        raise ValueError("GradNormConfig.num_tasks must equal the algorithm's num_tasks")
-    if config.use_task_weights:
-        raise NotImplementedError(
-            "GradNorm with use_task_weights: the reference's split actor loss multiplies by the unsplit closure "
-            "variable (mtsac.py:664), which the engine's per-task pass does not reproduce")
-    if task_shard is not None:
-        raise NotImplementedError(
-            "GradNorm on a task-sharded engine: the task weights are renormalised over every task, so all "
-            "tasks' gradients and losses must be on one engine")
+def _gradnorm_tail(opt_a, opt_c) -> None:
     for what, opt in (("actor", opt_a), ("critic", opt_c)):
         inner = opt.gradnorm_optimizer
         if inner.optimizer is not Optimizer.Adam or inner.requires_split_task_losses:
@@ -172,7 +128,42 @@ def _check_gradnorm(config: "MTSACConfig", task_shard) -> bool:
                 "gradient of the task weights by its zero norm (NaN weights in the reference)")
     if opt_a.asymmetry != opt_c.asymmetry:
         raise NotImplementedError("GradNorm: actor and critic asymmetry differ; the engine holds one value")
-    return True
+
+
+_SPLIT_ONLY_FOR_ACTOR = ("the reference hands the critic's optimizer per-task gradients only when the ACTOR's "
+                         "optimizer asks for split losses (mtsac.py:581), and {}'s shape assert fails on anything else")
+# mode -> _check_surgery's arguments: config class, display name, why not on one network, why not sharded, tail
+_SURGERY = {
+    "pcgrad": (PCGradConfig, "PCGrad",
+               "the reference itself cannot run it (mtsac.py:581 averages the critic's per-task gradients unless "
+               "the ACTOR's optimizer is PCGrad, and pcgrad's shape assert then fails)",
+               "the surgery needs every task's gradient of the whole network on one engine (the Gram matrix "
+               "couples all tasks)", _pcgrad_tail),
+    "cagrad": (CAGradConfig, "CAGrad", _SPLIT_ONLY_FOR_ACTOR.format("cagrad"),
+               "the weight search needs every task's gradient of the whole network on one engine (the Gram matrix "
+               "couples all tasks)"),
+    "gradnorm": (GradNormConfig, "GradNorm", _SPLIT_ONLY_FOR_ACTOR.format("gradnorm"),
+                 "the task weights are renormalised over every task, so all tasks' gradients and losses must be "
+                 "on one engine", _gradnorm_tail),
+}
+
+
+def _surgery_mode(config: "MTSACConfig", task_shard) -> str | None:
+    """The mode both optimizers ask for (a key of _SURGERY), None for plain Adam."""
+    on = [m for m, spec in _SURGERY.items() if _check_surgery(config, task_shard, *spec)]
+    return on[0] if on else None
+
+
+def _switch_on(engine: MTSACEngine, config: "MTSACConfig", mode: str | None, gradnorm_state=()) -> None:
+    """The engine's mode on, as the configs ask; ``gradnorm_state``: the (critic, actor) state to carry over."""
+    if mode == "pcgrad":
+        engine.set_pcgrad(True, config.actor_config.network_config.optimizer.cosine_sim_logs)
+    elif mode == "cagrad":
+        engine.set_cagrad(True)  # cagrad()'s defaults, as CAGradConfig.spawn calls it
+    elif mode == "gradnorm":  # initialised by the switch
+        engine.set_gradnorm(True, **_gradnorm_args(config))
+        for w, st in enumerate(gradnorm_state):
+            engine.set_gradnorm_state(w, st)
 
 
 def _gradnorm_args(config: "MTSACConfig") -> dict:
@@ -202,9 +193,13 @@ class MTSAC(OffPolicyAlgorithm):
         self._buffer = None  # the replay buffer living in this engine, once spawned
         self.gamma, self.tau = config.gamma, config.tau
         self.target_entropy = -float(np.prod(env_config.action_space.shape))
-        self.pcgrad = False  # both optimizers PCGrad: the engine runs the gradient-surgery step
-        self.cagrad = False  # both optimizers CAGrad: the same step with CAGrad's solve
-        self.gradnorm = False  # both optimizers GradNorm: the same step with GradNorm's stateful solve
+        # both optimizers PCGrad, CAGrad or GradNorm ("pcgrad", "cagrad", "gradnorm"): the engine runs the
+        # gradient-surgery step with that method's solve
+        self.surgery: str | None = None
+
+    pcgrad = property(lambda self: self.surgery == "pcgrad")
+    cagrad = property(lambda self: self.surgery == "cagrad")
+    gradnorm = property(lambda self: self.surgery == "gradnorm")
 
     # ------------------------------------------------------------------ construction
     @staticmethod
@@ -217,9 +212,7 @@ class MTSAC(OffPolicyAlgorithm):
         net_a, net_c = config.actor_config.network_config, config.critic_config.network_config
         _check_supported(net_a, "actor")
         _check_supported(net_c, "critic")
-        pcgrad = _check_pcgrad(config, task_shard)
-        cagrad = _check_cagrad(config, task_shard)
-        gradnorm = _check_gradnorm(config, task_shard)
+        surgery = _surgery_mode(config, task_shard)
         if task_shard is not None:
             raise NotImplementedError("task sharding is driven through mtrl_amd.shard, not this trainer")
         T = config.num_tasks
@@ -238,12 +231,7 @@ class MTSAC(OffPolicyAlgorithm):
             batch_per_task=128, capacity=128, precision=L.PRECISIONS[precision], noise_seed=seed + 1,
         )
         eng = MTSACEngine(make_config(**kw), device=device)
-        if pcgrad:
-            eng.set_pcgrad(True, net_a.optimizer.cosine_sim_logs)
-        if cagrad:
-            eng.set_cagrad(True)  # cagrad()'s defaults, as CAGradConfig.spawn calls it
-        if gradnorm:
-            eng.set_gradnorm(True, **_gradnorm_args(config))
+        _switch_on(eng, config, surgery)
         a, q = init_mtsac(T, obs_dim, act_dim, net_a.width, net_a.depth, net_c.width, net_c.depth,
                           config.num_critics, seed=seed)
         eng.set_params(L.ACTOR, a)
@@ -252,9 +240,7 @@ class MTSAC(OffPolicyAlgorithm):
         print("Actor Params:", eng.param_count(L.ACTOR))
         print("Critic Params:", eng.param_count(L.CRITIC))
         agent = MTSAC(config, env_config, seed, eng, kw)
-        agent.pcgrad = pcgrad
-        agent.cagrad = cagrad
-        agent.gradnorm = gradnorm
+        agent.surgery = surgery
         return agent
 
     def _rebuild(self, **changes) -> None:
@@ -272,14 +258,7 @@ class MTSAC(OffPolicyAlgorithm):
         old = self.engine
         self.engine = MTSACEngine(make_config(**self._cfg_kwargs), device=old.device)
         old.close()
-        if self.pcgrad:
-            self.engine.set_pcgrad(True, self.config.actor_config.network_config.optimizer.cosine_sim_logs)
-        if self.cagrad:
-            self.engine.set_cagrad(True)
-        if self.gradnorm:  # re-initialised by the switch; the state so far is carried over
-            self.engine.set_gradnorm(True, **_gradnorm_args(self.config))
-            for w, st in enumerate(gn_state):
-                self.engine.set_gradnorm_state(w, st)
+        _switch_on(self.engine, self.config, self.surgery, gn_state)
         for w, v in keep.items():
             self.engine.set_params(w, v)
         for i, c in enumerate(counts):
@@ -336,13 +315,13 @@ class MTSAC(OffPolicyAlgorithm):
         if n != self._cfg_kwargs["batch_per_task"]:  # raises once a buffer lives in the engine
             self._rebuild(batch_per_task=n, capacity=max(self._cfg_kwargs["capacity"], n))
         self.engine.update(tuple(data))
-        return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad, self.gradnorm)
+        return self, _DeviceLogs(self.engine, self.surgery)
 
     def update_from_buffer(self, replay_buffer, batch_size: int, want_logs: bool):
         if getattr(replay_buffer, "engine", None) is self.engine and batch_size // self.num_tasks == \
                 self._cfg_kwargs["batch_per_task"]:
             self.engine.update_many(1)  # device sampling + update, no host round trip
-            return self, _DeviceLogs(self.engine, self.pcgrad, self.cagrad, self.gradnorm)
+            return self, _DeviceLogs(self.engine, self.surgery)
         return super().update_from_buffer(replay_buffer, batch_size, want_logs)
 
     def compute_weights(self, data):

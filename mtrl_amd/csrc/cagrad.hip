@@ -14,17 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "wave_sum.h"
 
 namespace mtsac {
 namespace {
 
 constexpr int TP = 64;  // task rows padded (engine limit: 64 tasks)
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __device__ inline double wave_max(double v) {
 #pragma unroll

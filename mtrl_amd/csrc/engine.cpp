@@ -69,6 +69,7 @@ struct Net {
   long long ms_hb = 0, ms_hW = 0, ms_b = 0, ms_W[MAXD] = {};  // member strides
   long long n_flat = 0, trunk_off = 0, n_params = 0;
   std::vector<std::pair<long long, long long>> leaves;  // (offset, count) in flax order
+  std::vector<long long> dense;  // leaf k's offset with the leaves back to back (no padding); [leaves.size()] = n_params
   float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr, *tgt = nullptr;
   // transposed hidden kernels W_i^T ([E][out][in], i >= 1) of p (wt[0]) and tgt (wt[1]): the
   // trunk forward runs as an NT product against them (k-contiguous operands on both sides)
@@ -138,6 +139,8 @@ struct Net {
       fan = W;
     }
     n_flat = o;
+    dense.assign(1, 0);
+    for (const auto& lf : leaves) dense.push_back(dense.back() + lf.second);
   }
 };
 
@@ -437,9 +440,16 @@ struct mtsac_engine {
                          "): its split-K workspaces were sized for the old one; restore it or create a new engine");
   }
 
-  ~mtsac_engine() {
+  // the captured step graph, if any, is stale: the next mtsac_update_many captures a new one
+  void drop_graph() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
+    gexec = nullptr;
+    graph = nullptr;
+  }
+
+  ~mtsac_engine() {
+    drop_graph();
     for (auto& t : tl) {
       (void)hipEventDestroy(t.a);
       (void)hipEventDestroy(t.b);
@@ -1822,17 +1832,6 @@ struct mtsac_engine {
   float* ps_thr = nullptr;
   static constexpr int PS_GRID = 512;
 
-  static std::vector<long long> dense_offsets(const Net& net) {  // flax leaf offsets, no padding
-    std::vector<long long> off;
-    long long o = 0;
-    for (const auto& lf : net.leaves) {
-      off.push_back(o);
-      o += lf.second;
-    }
-    off.push_back(o);
-    return off;
-  }
-
   int ensure_task_grad_buffers() {
     int rc = 0;
     for (int w = 0; w < 2; ++w) {
@@ -1853,7 +1852,7 @@ struct mtsac_engine {
 
   // dW_t, db_t of trunk layer i for every task t (one batched TN GEMM per ensemble member)
   void task_wgrad(Net& net, int w, const float* X, int ldx, float** acts, float** dz, int i) {
-    const std::vector<long long> off = dense_offsets(net);
+    const std::vector<long long>& off = net.dense;
     const int fan = i == 0 ? net.in_dim : net.width;
     const int n_rows = B / T_l;
     for (int e = 0; e < net.E; ++e) {
@@ -1879,7 +1878,7 @@ struct mtsac_engine {
 
   // the task's own head block (bias, kernel) of the padded gradient buffer into its dense row
   void task_heads(Net& net, int w) {
-    const std::vector<long long> off = dense_offsets(net);
+    const std::vector<long long>& off = net.dense;
     scatter_task_blocks(net.g, net.off_hb, net.ms_hb, tg[w], tgP[w], off[0], (long long)T_l * net.hd, net.E, T_l,
                         net.hd, cur);
     scatter_task_blocks(net.g, net.off_hW, net.ms_hW, tg[w], tgP[w], off[1], (long long)T_l * net.width * net.hd,
@@ -1997,7 +1996,7 @@ struct mtsac_engine {
         ag.ld_a_data = ld_c;
         ag.explore_scale = 2.0f / ((float)n_rows * (float)A);
         ag.row_loss = row_c;
-        ag.row_explore = pc_row_e;
+        ag.row_explore = sg.row_e;
       }
       action_grad(ag, cur);
     }
@@ -2069,7 +2068,7 @@ struct mtsac_engine {
   // so optimize() -- clip, Adam, Polyak, planes -- runs unchanged.  Eager, on the main stream.
   //
   // CAGrad (CAGradConfig: cagrad -> clip_by_global_norm -> adam; mtrl/optim/cagrad.py) is the same step
-  // with another solve between the Gram and the combine (cagrad.hip): `surgery` picks it.
+  // with another solve between the Gram and the combine (cagrad.hip): `sg.kind` picks it.
   //
   // GradNorm (GradNormConfig: gradnorm -> clip_by_global_norm -> adam; mtrl/optim/gradnorm.py) is the same
   // step again (gradnorm.hip): it also consumes the per-task loss values (task_losses over the split
@@ -2077,107 +2076,159 @@ struct mtsac_engine {
   // the inner Adam's moments on the device, the inner count here.
   enum { SURGERY_NONE = 0, SURGERY_PCGRAD = 1, SURGERY_CAGRAD = 2, SURGERY_GRADNORM = 3 };
   static constexpr int CA_MAX_ITERS = 1024;  // obj_hist slots per network
-  int surgery = SURGERY_NONE;
-  bool pc_cos = false, pc_pinned = false, pc_graph_before = true;
-  double *pc_gram = nullptr, *pc_c = nullptr;
-  float *pc_w = nullptr, *pc_logs = nullptr, *pc_row_e = nullptr;  // [2][64], [2][8] (0 critic, 1 actor), [B]
-  int *pc_perm = nullptr, *pc_pin = nullptr;                       // [2][64] orders used / pinned
-  int ca_iters = 21;
-  double ca_c = 0.5, ca_lr = 25.0, ca_momentum = 0.5;
-  bool ca_cos = false;
-  float* ca_tw = nullptr;                        // [2][64] task weights
-  double *ca_hist = nullptr, *ca_w0 = nullptr;   // [2][CA_MAX_ITERS] objectives, [64] a kernel-alone start
-  // GradNorm: slot 0 critic, 1 actor, 2 the kernel-alone call's
-  float *gn_state = nullptr, *gn_loss = nullptr;  // [3][4][64] task_weights, original_losses, mu, nu; [3][64]
-  long long gn_count[2] = {0, 0};                 // inner Adam counts
-  double gn_asym = 0.12, gn_lr[2] = {3e-4, 3e-4}, gn_eps[2] = {1e-5, 1e-5}, gn_max_norm[2] = {1.0, 1.0};
-  bool gn_clip[2] = {true, true}, gn_weighted = false, gn_ready = false;  // ready: initialised once
+  // Device blocks of the surgery: rows of TS floats (the 64-task limit) and log slots of LOG_SLOT floats,
+  // one per network (0 critic, 1 actor); GradNorm's state is GN_ROWS rows per slot (task_weights,
+  // original_losses, mu, nu), its slots and the loss rows' 0 critic, 1 actor, GN_ALONE the kernel-alone call's
+  static constexpr int TS = 64, LOG_SLOT = 8, GN_ROWS = 4, GN_ALONE = 2;
+  struct Surgery {
+    int kind = SURGERY_NONE;
+    bool cosine = false;        // PCGrad, CAGrad: the cosine-similarity logs
+    bool graph_before = true;   // use_graph as it was when a mode went on from none; back when it goes off
+    bool pinned = false;        // PCGrad: the step takes the orders in `pin`
+    bool gn_ready = false;      // GradNorm's state was initialised once
+    // the step's solve parameters as the setters left them (the device pointers are bound at every solve)
+    CagradSolve ca{};
+    GradnormSolve gn[2]{};      // count: the inner Adam's, before the next step
+    double *gram = nullptr, *c = nullptr;                     // [TS][TS] Gram, PCGrad's coefficient workspace
+    float *w = nullptr, *logs = nullptr, *row_e = nullptr;    // [2][TS], [2][LOG_SLOT], [B]
+    int *perm = nullptr, *pin = nullptr;                      // [2][TS] orders used / pinned
+    float* ca_tw = nullptr;                                   // [2][TS] task weights
+    double *ca_hist = nullptr, *ca_w0 = nullptr;  // [2][CA_MAX_ITERS] objectives, [TS] a kernel-alone start
+    float *gn_state = nullptr, *gn_loss = nullptr;            // [3][GN_ROWS][TS], [3][TS]
+    float* w_of(int net) const { return w + TS * net; }
+    float* logs_of(int net) const { return logs + LOG_SLOT * net; }
+    int* pin_of(int net) const { return pin + TS * net; }
+    float* gn_state_of(int slot) const { return gn_state + GN_ROWS * TS * slot; }
+    float* gn_loss_of(int slot) const { return gn_loss + TS * slot; }
+  } sg;
 
-  int ensure_pcgrad_buffers() {
+  int ensure_surgery_buffers() {
     int rc = 0;
-    if (pc_gram) return 0;
-    if ((rc = alloc(&pc_gram, 64 * 64)) || (rc = alloc(&pc_c, 64 * 64)) || (rc = alloc(&pc_w, 2 * 64)) ||
-        (rc = alloc(&pc_logs, 2 * 8)) || (rc = alloc(&pc_row_e, (size_t)B)) || (rc = alloc(&pc_perm, 2 * 64)) ||
-        (rc = alloc(&pc_pin, 2 * 64)) || (rc = alloc(&ca_tw, 2 * 64)) ||
-        (rc = alloc(&ca_hist, 2 * (size_t)CA_MAX_ITERS)) || (rc = alloc(&ca_w0, 64)) ||
-        (rc = alloc(&gn_state, 3 * 4 * 64)) || (rc = alloc(&gn_loss, 3 * 64)))
+    if (sg.gram) return 0;
+    if ((rc = alloc(&sg.gram, TS * TS)) || (rc = alloc(&sg.c, TS * TS)) || (rc = alloc(&sg.w, 2 * TS)) ||
+        (rc = alloc(&sg.logs, 2 * LOG_SLOT)) || (rc = alloc(&sg.row_e, (size_t)B)) || (rc = alloc(&sg.perm, 2 * TS)) ||
+        (rc = alloc(&sg.pin, 2 * TS)) || (rc = alloc(&sg.ca_tw, 2 * TS)) ||
+        (rc = alloc(&sg.ca_hist, 2 * (size_t)CA_MAX_ITERS)) || (rc = alloc(&sg.ca_w0, TS)) ||
+        (rc = alloc(&sg.gn_state, 3 * GN_ROWS * TS)) || (rc = alloc(&sg.gn_loss, 3 * TS)))
       return rc;
     return hipDeviceSynchronize() == hipSuccess ? 0 : fail(-5, "device synchronize");
   }
 
-  PcgradLeaves pc_leaves(const Net& net) const {
+  PcgradLeaves surgery_leaves(const Net& net) const {
     PcgradLeaves lv{};
-    const std::vector<long long> off = dense_offsets(net);
     lv.n = (int)net.leaves.size();
     for (int k = 0; k < lv.n; ++k) {
-      lv.dense[k] = off[k];
+      lv.dense[k] = net.dense[k];
       lv.padded[k] = net.leaves[k].first;
     }
     return lv;
   }
 
-  void pc_gram_of(int w) {
-    task_gram(tg[w], T_l, tgP[w], task_gram_parts(tgP[w], PS_GRID), ps_gram_part, pc_gram, cur);
+  void gram_of(int w) {
+    task_gram(tg[w], T_l, tgP[w], task_gram_parts(tgP[w], PS_GRID), ps_gram_part, sg.gram, cur);
   }
 
-  void pc_solve_of(int w, const int* pinned, bool cosine) {
-    PcgradSolve s{};
-    s.gram = pc_gram;
+  // One solve on sg.gram for network w.  `s` carries the method's own parameters (the step's stored ones or
+  // a kernel-alone call's arguments); the device slots are bound here: every method leaves its combine
+  // weights in w_of(w) and its scalars (|mean_t g_t| in [5]) in logs_of(w).
+  template <class S>
+  S bound(S s, int w) const {
+    s.gram = sg.gram;
     s.T = T_l;
-    s.pinned = pinned;
+    s.w = sg.w_of(w);
+    s.logs = sg.logs_of(w);
+    return s;
+  }
+  void solve(const PcgradSolve& p, int w) {  // p: pinned, cosine_logs
+    PcgradSolve s = bound(p, w);
     s.seed = cfg.noise_seed;
     s.counter = counter;
     s.stream_id = 7 + w;
-    s.cosine_logs = cosine ? 1 : 0;
-    s.ws_c = pc_c;
-    s.perm_out = pc_perm + 64 * w;
-    s.w = pc_w + 64 * w;
-    s.logs = pc_logs + 8 * w;
+    s.ws_c = sg.c;
+    s.perm_out = sg.perm + TS * w;
     pcgrad_solve(s, cur);
   }
-
-  // CAGrad's solve on pc_gram: combine weights into the pc_w slot, the four state scalars (+ the best
-  // iterate's index and |mean_t g_t|) into the pc_logs slot
-  void ca_solve_of(int w, double c, int iters, double lr, double momentum, const double* w0, bool cosine) {
-    CagradSolve s{};
-    s.gram = pc_gram;
-    s.T = T_l;
-    s.iters = iters;
-    s.c = c;
-    s.lr = lr;
-    s.momentum = momentum;
-    s.w0 = w0;
-    s.cosine_logs = cosine ? 1 : 0;
-    s.w = pc_w + 64 * w;
-    s.task_weights = ca_tw + 64 * w;
-    s.logs = pc_logs + 8 * w;
-    s.obj_hist = ca_hist + (size_t)CA_MAX_ITERS * w;
+  void solve(const CagradSolve& p, int w) {  // p: iters, c, lr, momentum, w0, cosine_logs
+    CagradSolve s = bound(p, w);
+    s.task_weights = sg.ca_tw + TS * w;
+    s.obj_hist = sg.ca_hist + (size_t)CA_MAX_ITERS * w;
     cagrad_solve(s, cur);
   }
-
-  // GradNorm's solve on pc_gram with the state and losses of slot `slot`: combine weights into the pc_w
-  // slot of network w, gradnorm_loss and |mean_t g_t| into its pc_logs slot; count: the advanced one
-  void gn_solve_of(int w, int slot, double asymmetry, bool clip, double lr, double eps, double max_norm,
-                   bool weighted, long long count) {
-    GradnormSolve s{};
-    s.gram = pc_gram;
-    s.T = T_l;
-    s.losses = gn_loss + 64 * slot;
-    s.asymmetry = asymmetry;
-    s.per_task_clip = clip ? 1 : 0;
-    s.lr = lr;
-    s.eps = eps;
-    s.max_norm = max_norm;
-    s.weighted = weighted ? 1 : 0;
-    s.count = count;
-    float* stt = gn_state + 4 * 64 * slot;
+  // p: asymmetry, per_task_clip, lr, eps, max_norm, weighted, count (the advanced one); the state and the
+  // losses are slot `slot`'s
+  void solve(const GradnormSolve& p, int w, int slot) {
+    GradnormSolve s = bound(p, w);
+    s.losses = sg.gn_loss_of(slot);
+    float* stt = sg.gn_state_of(slot);
     s.task_weights = stt;
-    s.original_losses = stt + 64;
-    s.mu = stt + 128;
-    s.nu = stt + 192;
-    s.w = pc_w + 64 * w;
-    s.logs = pc_logs + 8 * w;
+    s.original_losses = stt + TS;
+    s.mu = stt + 2 * TS;
+    s.nu = stt + 3 * TS;
     gradnorm_solve(s, cur);
+  }
+
+  // Gram and solve of network `which` on the main stream, as the kernel-alone entries run them; then the
+  // combine weights ([T]) and the whole log slot ([LOG_SLOT]) back
+  template <class S, class... Slot>
+  int solve_alone(int which, const S& p, float* w_out, float* logs_out, Slot... slot) {
+    cur = st;
+    gram_of(which);
+    solve(p, which, slot...);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(w_out, sg.w_of(which), sizeof(float) * T_l, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(logs_out, sg.logs_of(which), sizeof(float) * LOG_SLOT, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+  }
+
+  // rows[r][0 .. cols) <- dev[ld * r + .] for r < k (to_device: the other way, the rows' tails zeroed), the
+  // main stream's work done on return
+  int copy_rows(float* dev, int ld, float* const* rows, int k, int cols, bool to_device = false) {
+    std::vector<float> blk((size_t)ld * k, 0.f);
+    if (to_device)
+      for (int r = 0; r < k; ++r) std::copy(rows[r], rows[r] + cols, blk.begin() + (size_t)ld * r);
+    else HIP_TRY(hipMemcpyAsync(blk.data(), dev, sizeof(float) * blk.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (to_device) HIP_TRY(hipMemcpy(dev, blk.data(), sizeof(float) * blk.size(), hipMemcpyHostToDevice));
+    else
+      for (int r = 0; r < k; ++r) std::copy(blk.begin() + (size_t)ld * r, blk.begin() + (size_t)ld * r + cols, rows[r]);
+    return 0;
+  }
+
+  // The shared mode switch behind mtsac_set_pcgrad / _cagrad / _gradnorm.  Off: a no-op unless `kind` is on.
+  int surgery_leave(int kind) {
+    HIP_TRY(hipStreamSynchronize(st));
+    if (sg.kind == kind) {
+      use_graph = sg.graph_before;
+      sg.kind = SURGERY_NONE;
+    }
+    return 0;
+  }
+  // On, before the method's own argument checks: nothing is allocated or changed yet
+  int surgery_precheck(int kind) const {
+    static const char* const names[] = {"", "PCGrad", "CAGrad", "GradNorm"};
+    static const char* const undo[] = {"", "mtsac_set_pcgrad", "mtsac_set_cagrad", "mtsac_set_gradnorm"};
+    const char* name = names[kind];
+    if (sg.kind && sg.kind != kind)
+      return fail(-16, std::string(names[sg.kind]) + " is on (" + undo[sg.kind] + "(0) first)");
+    if (T_l != T_g || sharded()) return fail(-95, std::string(name) + " needs every task on one engine (unsharded)");
+    if (cfg.use_task_weights)
+      return fail(-95, std::string(name) +
+                           " with use_task_weights: the reference's split losses multiply by the unsplit weights");
+    if (T_l > TS) return fail(-22, std::string(name) + ": at most 64 tasks");
+    return 0;
+  }
+  // On, after them: buffers, the mode; the caller then stores its own parameters
+  int surgery_commit(int kind) {
+    int rc = ensure_task_grad_buffers();
+    if (!rc) rc = ensure_surgery_buffers();
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    drop_graph();  // a captured plain step is not this mode's step
+    if (!sg.kind) sg.graph_before = use_graph;
+    use_graph = false;
+    sg.kind = kind;
+    return 0;
   }
 
   // the per-task loss values of network w from the split pass's per-row terms: the critic's row_a (sum over
@@ -2185,27 +2236,35 @@ struct mtsac_engine {
   // term taken off by action_grad) over n
   void gn_losses_of(int w) {
     const int n_rows = B / T_l;
-    if (w == 0) task_losses(row_a, T_l, n_rows, 1.0 / ((double)critic.E * (double)n_rows), gn_loss, cur);
-    else task_losses(row_c, T_l, n_rows, 1.0 / (double)n_rows, gn_loss + 64, cur);
+    if (w == 0) task_losses(row_a, T_l, n_rows, 1.0 / ((double)critic.E * (double)n_rows), sg.gn_loss_of(0), cur);
+    else task_losses(row_c, T_l, n_rows, 1.0 / (double)n_rows, sg.gn_loss_of(1), cur);
   }
 
   // Gram, solve, combine of network w (0 critic, 1 actor): Net::g = mean_i g_i^pc (PCGrad), or CAGrad's
   // or GradNorm's update
-  void pc_surgery(Net& net, int w) {
-    if (surgery == SURGERY_GRADNORM) gn_losses_of(w);
-    pc_gram_of(w);
-    if (surgery == SURGERY_GRADNORM)
-      gn_solve_of(w, w, gn_asym, gn_clip[w], gn_lr[w], gn_eps[w], gn_max_norm[w], gn_weighted, ++gn_count[w]);
-    else if (surgery == SURGERY_CAGRAD) ca_solve_of(w, ca_c, ca_iters, ca_lr, ca_momentum, nullptr, ca_cos);
-    else pc_solve_of(w, pc_pinned ? pc_pin + 64 * w : nullptr, pc_cos);
-    task_combine(tg[w], pc_w + 64 * w, T_l, tgP[w], pc_leaves(net), net.g, cur);
+  void surgery_of(Net& net, int w) {
+    if (sg.kind == SURGERY_GRADNORM) gn_losses_of(w);
+    gram_of(w);
+    if (sg.kind == SURGERY_GRADNORM) {
+      ++sg.gn[w].count;
+      solve(sg.gn[w], w, w);
+    } else if (sg.kind == SURGERY_CAGRAD) {
+      CagradSolve s = sg.ca;
+      s.cosine_logs = sg.cosine;
+      solve(s, w);
+    } else {
+      PcgradSolve s{};
+      s.pinned = sg.pinned ? sg.pin_of(w) : nullptr;
+      s.cosine_logs = sg.cosine;
+      solve(s, w);
+    }
+    task_combine(tg[w], sg.w_of(w), T_l, tgP[w], surgery_leaves(net), net.g, cur);
   }
 
   // the other tasks' head blocks of every row stay zero: only the rows' head ranges are cleared (the
   // trunk leaves are stored whole by the per-task weight grads)
-  void pc_clear_heads(const Net& net, int w) {
-    const std::vector<long long> off = dense_offsets(net);
-    (void)hipMemset2DAsync(tg[w], sizeof(float) * tgP[w], 0, sizeof(float) * off[2], T_l, cur);
+  void clear_task_heads(const Net& net, int w) {
+    (void)hipMemset2DAsync(tg[w], sizeof(float) * tgP[w], 0, sizeof(float) * net.dense[2], T_l, cur);
   }
 
   void pcgrad_step(bool device_batch, bool device_noise) {
@@ -2215,23 +2274,23 @@ struct mtsac_engine {
     have_prev = false;
     tg_prepare(device_batch);
     // critic (mtsac.py:513-621, split losses): per-task gradients, surgery, clip + Adam + Polyak
-    pc_clear_heads(critic, 0);
+    clear_task_heads(critic, 0);
     tg_critic(device_noise, true);
-    pc_surgery(critic, 0);
+    surgery_of(critic, 0);
     optimize(critic, cfg.critic_lr, cfg.critic_max_grad_norm, true, 0);
     refresh_wt(critic, critic.p, 0, cur, true);
     refresh_wt(critic, critic.tgt, 1, cur, true);
     // actor through the UPDATED critic (mtsac.py:623-711)
-    pc_clear_heads(actor, 1);
+    clear_task_heads(actor, 1);
     tg_actor(device_noise, true);
-    pc_surgery(actor, 1);
+    surgery_of(actor, 1);
     optimize(actor, cfg.actor_lr, cfg.actor_max_grad_norm, false, 1);
     refresh_wt(actor, actor.p, 0, cur, true);
     // temperature, parameter norms, logs; then the slots the surgery changes: the gradient magnitudes
     // are the pre-surgery |mean_t g_t| (the optimizer's clip saw the combined gradient's norm)
     StepFinish f = finish_params(alpha_params());
     step_finish(f, cur);
-    pcgrad_logs(pc_logs, pc_logs + 8, pc_row_e, B, logs, cur);
+    pcgrad_logs(sg.logs_of(0), sg.logs_of(1), sg.row_e, B, logs, cur);
     cur = st;
   }
 
@@ -2308,6 +2367,26 @@ struct mtsac_engine {
       gp.pc_ld = (int)critic.xld;
     }
     return gp;
+  }
+
+  // a caller's batch and noise (either may be null: the device's own) into the upload buffers on the main
+  // stream; the host pointers are borrowed until the stream is synchronized
+  int upload(const mtsac_batch* b, const float* eps_next, const float* eps_cur) {
+    if ((eps_next == nullptr) != (eps_cur == nullptr)) return fail(-22, "inject both eps_next and eps_cur or neither");
+    if (b) {
+      if (!b->observations || !b->actions || !b->next_observations || !b->dones || !b->rewards)
+        return fail(-22, "incomplete batch");
+      HIP_TRY(hipMemcpyAsync(u_obs, b->observations, sizeof(float) * B * D, hipMemcpyDefault, st));
+      HIP_TRY(hipMemcpyAsync(u_nobs, b->next_observations, sizeof(float) * B * D, hipMemcpyDefault, st));
+      HIP_TRY(hipMemcpyAsync(u_act, b->actions, sizeof(float) * B * A, hipMemcpyDefault, st));
+      HIP_TRY(hipMemcpyAsync(u_done, b->dones, sizeof(float) * B, hipMemcpyDefault, st));
+      HIP_TRY(hipMemcpyAsync(u_rew, b->rewards, sizeof(float) * B, hipMemcpyDefault, st));
+    }
+    if (eps_next) {
+      HIP_TRY(hipMemcpyAsync(eps_n, eps_next, sizeof(float) * B * A, hipMemcpyDefault, st));
+      HIP_TRY(hipMemcpyAsync(eps_c, eps_cur, sizeof(float) * B * A, hipMemcpyDefault, st));
+    }
+    return 0;
   }
 
   int check_err() {
@@ -3093,23 +3172,9 @@ int mtsac_sample(mtsac_engine* h, int64_t* indices, float* obs, float* actions, 
 int mtsac_update(mtsac_engine* h, const mtsac_batch* b, const float* eps_next, const float* eps_cur) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
-  if ((eps_next == nullptr) != (eps_cur == nullptr)) return fail(-22, "inject both eps_next and eps_cur or neither");
-  const int B = h->B, D = h->D, A = h->A;
-  if (b) {
-    if (!b->observations || !b->actions || !b->next_observations || !b->dones || !b->rewards)
-      return fail(-22, "incomplete batch");
-    HIP_TRY(hipMemcpyAsync(h->u_obs, b->observations, sizeof(float) * B * D, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_nobs, b->next_observations, sizeof(float) * B * D, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_act, b->actions, sizeof(float) * B * A, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_done, b->dones, sizeof(float) * B, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_rew, b->rewards, sizeof(float) * B, hipMemcpyDefault, h->st));
-  }
-  if (eps_next) {
-    HIP_TRY(hipMemcpyAsync(h->eps_n, eps_next, sizeof(float) * B * A, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->eps_c, eps_cur, sizeof(float) * B * A, hipMemcpyDefault, h->st));
-  }
+  if (int rc = h->upload(b, eps_next, eps_cur)) return rc;
   h->tl_next = 0;
-  if (h->surgery) {
+  if (h->sg.kind) {
     if (h->sharded()) return fail(-95, "PCGrad / CAGrad / GradNorm needs every task on one engine (unsharded)");
     h->pcgrad_step(b == nullptr, eps_next == nullptr);
   } else {
@@ -3132,23 +3197,9 @@ int mtsac_task_gradients(mtsac_engine* h, const mtsac_batch* b, const float* eps
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
   if (h->T_l != h->T_g) return fail(-95, "per-task gradients need every task on one engine (unsharded)");
-  if ((eps_next == nullptr) != (eps_cur == nullptr)) return fail(-22, "inject both eps_next and eps_cur or neither");
   int rc = h->ensure_task_grad_buffers();
+  if (!rc) rc = h->upload(b, eps_next, eps_cur);
   if (rc) return rc;
-  const int B = h->B, D = h->D, A = h->A;
-  if (b) {
-    if (!b->observations || !b->actions || !b->next_observations || !b->dones || !b->rewards)
-      return fail(-22, "incomplete batch");
-    HIP_TRY(hipMemcpyAsync(h->u_obs, b->observations, sizeof(float) * B * D, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_nobs, b->next_observations, sizeof(float) * B * D, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_act, b->actions, sizeof(float) * B * A, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_done, b->dones, sizeof(float) * B, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->u_rew, b->rewards, sizeof(float) * B, hipMemcpyDefault, h->st));
-  }
-  if (eps_next) {
-    HIP_TRY(hipMemcpyAsync(h->eps_n, eps_next, sizeof(float) * B * A, hipMemcpyDefault, h->st));
-    HIP_TRY(hipMemcpyAsync(h->eps_c, eps_cur, sizeof(float) * B * A, hipMemcpyDefault, h->st));
-  }
   const bool timing = h->timing;
   h->timing = false;
   h->task_grads(b == nullptr, eps_next == nullptr);
@@ -3238,35 +3289,11 @@ int mtsac_task_gradient_stats(mtsac_engine* h, int which, const float* threshold
 // ---------------------------------------------------------------- PCGrad
 int mtsac_set_pcgrad(mtsac_engine* h, int32_t on, int32_t cosine_sim_logs) {
   if (!h) return fail(-22, "null engine");
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->surgery == mtsac_engine::SURGERY_PCGRAD) {
-      h->use_graph = h->pc_graph_before;
-      h->surgery = mtsac_engine::SURGERY_NONE;
-    }
-    return 0;
-  }
-  if (h->surgery == mtsac_engine::SURGERY_CAGRAD) return fail(-16, "CAGrad is on (mtsac_set_cagrad(0) first)");
-  if (h->surgery == mtsac_engine::SURGERY_GRADNORM)
-    return fail(-16, "GradNorm is on (mtsac_set_gradnorm(0) first)");
-  if (h->T_l != h->T_g || h->sharded()) return fail(-95, "PCGrad needs every task on one engine (unsharded)");
-  if (h->cfg.use_task_weights)
-    return fail(-95, "PCGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
-  if (h->T_l > 64) return fail(-22, "PCGrad: at most 64 tasks");
-  int rc = h->ensure_task_grad_buffers();
-  if (!rc) rc = h->ensure_pcgrad_buffers();
+  if (!on) return h->surgery_leave(mtsac_engine::SURGERY_PCGRAD);
+  int rc = h->surgery_precheck(mtsac_engine::SURGERY_PCGRAD);
+  if (!rc) rc = h->surgery_commit(mtsac_engine::SURGERY_PCGRAD);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  if (h->gexec) {  // a captured plain step is not this mode's step
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
-  if (!h->surgery) h->pc_graph_before = h->use_graph;
-  h->use_graph = false;
-  h->surgery = mtsac_engine::SURGERY_PCGRAD;
-  h->pc_cos = cosine_sim_logs != 0;
+  h->sg.cosine = cosine_sim_logs != 0;
   return 0;
 }
 
@@ -3281,38 +3308,35 @@ static bool is_perm(const int32_t* p, int T) {
 
 int mtsac_pcgrad_set_order(mtsac_engine* h, const int32_t* critic_perm, const int32_t* actor_perm) {
   if (!h) return fail(-22, "null engine");
-  if (!h->pc_gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
+  if (!h->sg.gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
   if ((critic_perm == nullptr) != (actor_perm == nullptr)) return fail(-22, "pin both orders or neither");
   HIP_TRY(hipStreamSynchronize(h->st));
   if (!critic_perm) {
-    h->pc_pinned = false;
+    h->sg.pinned = false;
     return 0;
   }
   const int T = h->T_l;
   if (!is_perm(critic_perm, T) || !is_perm(actor_perm, T)) return fail(-22, "an order must be a permutation of 0..T-1");
-  HIP_TRY(hipMemcpy(h->pc_pin, critic_perm, sizeof(int) * T, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->pc_pin + 64, actor_perm, sizeof(int) * T, hipMemcpyHostToDevice));
-  h->pc_pinned = true;
+  HIP_TRY(hipMemcpy(h->sg.pin_of(0), critic_perm, sizeof(int) * T, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->sg.pin_of(1), actor_perm, sizeof(int) * T, hipMemcpyHostToDevice));
+  h->sg.pinned = true;
   return 0;
 }
 
 int mtsac_pcgrad_get_order(mtsac_engine* h, int32_t* critic_perm, int32_t* actor_perm) {
   if (!h || !critic_perm || !actor_perm) return fail(-22, "null argument");
-  if (!h->pc_gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
+  if (!h->sg.gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
   HIP_TRY(hipStreamSynchronize(h->st));
-  HIP_TRY(hipMemcpy(critic_perm, h->pc_perm, sizeof(int) * h->T_l, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(actor_perm, h->pc_perm + 64, sizeof(int) * h->T_l, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(critic_perm, h->sg.perm, sizeof(int) * h->T_l, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(actor_perm, h->sg.perm + mtsac_engine::TS, sizeof(int) * h->T_l, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int mtsac_get_pcgrad_logs(mtsac_engine* h, float* out) {
   if (!h || !out) return fail(-22, "null argument");
-  if (!h->pc_gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
-  float l[16];
-  HIP_TRY(hipMemcpyAsync(l, h->pc_logs, sizeof(l), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  for (int w = 0; w < 2; ++w)
-    for (int k = 0; k < 5; ++k) out[5 * w + k] = l[8 * w + k];
+  if (!h->sg.gram) return fail(-22, "PCGrad is not set up (mtsac_set_pcgrad)");
+  float* rows[2] = {out, out + 5};
+  if (int rc = h->copy_rows(h->sg.logs, mtsac_engine::LOG_SLOT, rows, 2, 5)) return rc;
   return h->check_err();
 }
 
@@ -3320,11 +3344,11 @@ int mtsac_task_gram(mtsac_engine* h, int which, double* gram) {
   int rc = task_grad_ready(h, which);
   if (rc) return rc;
   if (!gram) return fail(-22, "null argument");
-  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  if ((rc = h->ensure_surgery_buffers())) return rc;
   h->cur = h->st;
-  h->pc_gram_of(which);
+  h->gram_of(which);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(gram, h->pc_gram, sizeof(double) * h->T_l * h->T_l, hipMemcpyDeviceToHost, h->st));
+  HIP_TRY(hipMemcpyAsync(gram, h->sg.gram, sizeof(double) * h->T_l * h->T_l, hipMemcpyDeviceToHost, h->st));
   HIP_TRY(hipStreamSynchronize(h->st));
   return 0;
 }
@@ -3334,19 +3358,18 @@ int mtsac_task_pcgrad_solve(mtsac_engine* h, int which, const int32_t* perm, int
   int rc = task_grad_ready(h, which);
   if (rc) return rc;
   if (!perm || !w || !logs) return fail(-22, "null argument");
-  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  if ((rc = h->ensure_surgery_buffers())) return rc;
   const int T = h->T_l;
   if (!is_perm(perm, T)) return fail(-22, "an order must be a permutation of 0..T-1");
-  if (h->pc_pinned) return fail(-16, "orders are pinned for the training step (mtsac_pcgrad_set_order(NULL, NULL) first)");
+  if (h->sg.pinned) return fail(-16, "orders are pinned for the training step (mtsac_pcgrad_set_order(NULL, NULL) first)");
   HIP_TRY(hipStreamSynchronize(h->st));
-  HIP_TRY(hipMemcpy(h->pc_pin + 64 * which, perm, sizeof(int) * T, hipMemcpyHostToDevice));
-  h->cur = h->st;
-  h->pc_gram_of(which);
-  h->pc_solve_of(which, h->pc_pin + 64 * which, cosine_sim_logs != 0);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(w, h->pc_w + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(logs, h->pc_logs + 8 * which, sizeof(float) * 6, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
+  HIP_TRY(hipMemcpy(h->sg.pin_of(which), perm, sizeof(int) * T, hipMemcpyHostToDevice));
+  PcgradSolve s{};
+  s.pinned = h->sg.pin_of(which);
+  s.cosine_logs = cosine_sim_logs != 0;
+  float lg[mtsac_engine::LOG_SLOT];
+  if ((rc = h->solve_alone(which, s, w, lg))) return rc;
+  std::copy(lg, lg + 6, logs);
   return 0;
 }
 
@@ -3354,84 +3377,59 @@ int mtsac_task_combine(mtsac_engine* h, int which, const float* w, float* out_de
   int rc = task_grad_ready(h, which);
   if (rc) return rc;
   if (!w || !out_dense) return fail(-22, "null argument");
-  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  if ((rc = h->ensure_surgery_buffers())) return rc;
   Net& net = which == 0 ? h->critic : h->actor;
-  HIP_TRY(hipMemcpyAsync(h->pc_w + 64 * which, w, sizeof(float) * h->T_l, hipMemcpyHostToDevice, h->st));
+  HIP_TRY(hipMemcpyAsync(h->sg.w_of(which), w, sizeof(float) * h->T_l, hipMemcpyHostToDevice, h->st));
   h->cur = h->st;
-  task_combine(h->tg[which], h->pc_w + 64 * which, h->T_l, h->tgP[which], h->pc_leaves(net), net.g, h->st);
+  task_combine(h->tg[which], h->sg.w_of(which), h->T_l, h->tgP[which], h->surgery_leaves(net), net.g, h->st);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->st));
-  long long o = 0;  // the padded gradient buffer's leaves, as mtsac_get_params reads a parameter vector
-  for (auto& lf : net.leaves) {
-    HIP_TRY(hipMemcpy(out_dense + o, net.g + lf.first, sizeof(float) * lf.second, hipMemcpyDefault));
-    o += lf.second;
-  }
+  // the padded gradient buffer's leaves, as mtsac_get_params reads a parameter vector
+  for (size_t k = 0; k < net.leaves.size(); ++k)
+    HIP_TRY(hipMemcpy(out_dense + net.dense[k], net.g + net.leaves[k].first, sizeof(float) * net.leaves[k].second,
+                      hipMemcpyDefault));
   return 0;
 }
 
 // ---------------------------------------------------------------- CAGrad
-static int cagrad_args(double c, int32_t num_iterations, double learning_rate, double momentum) {
+// the arguments checked, then as the solve's parameter block (mtsac_set_cagrad's or a kernel-alone call's)
+static int cagrad_args(double c, int32_t num_iterations, double learning_rate, double momentum, CagradSolve* s) {
   if (num_iterations < 1) return fail(-22, "CAGrad: num_iterations must be at least 1");
   if (num_iterations > mtsac_engine::CA_MAX_ITERS) return fail(-22, "CAGrad: at most 1024 iterations");
   if (!std::isfinite(c) || c < 0.0) return fail(-22, "CAGrad: c must be finite and not negative");
   if (!std::isfinite(learning_rate) || !std::isfinite(momentum))
     return fail(-22, "CAGrad: learning rate and momentum must be finite");
+  *s = CagradSolve{};
+  s->c = c;
+  s->iters = num_iterations;
+  s->lr = learning_rate;
+  s->momentum = momentum;
   return 0;
 }
 
 int mtsac_set_cagrad(mtsac_engine* h, int32_t on, double c, int32_t num_iterations, double learning_rate,
                      double momentum, int32_t cosine_sim_logs) {
   if (!h) return fail(-22, "null engine");
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->surgery == mtsac_engine::SURGERY_CAGRAD) {
-      h->use_graph = h->pc_graph_before;
-      h->surgery = mtsac_engine::SURGERY_NONE;
-    }
-    return 0;
-  }
-  if (h->surgery == mtsac_engine::SURGERY_PCGRAD) return fail(-16, "PCGrad is on (mtsac_set_pcgrad(0) first)");
-  if (h->surgery == mtsac_engine::SURGERY_GRADNORM)
-    return fail(-16, "GradNorm is on (mtsac_set_gradnorm(0) first)");
-  if (h->T_l != h->T_g || h->sharded()) return fail(-95, "CAGrad needs every task on one engine (unsharded)");
-  if (h->cfg.use_task_weights)
-    return fail(-95, "CAGrad with use_task_weights: the reference's split losses multiply by the unsplit weights");
-  if (h->T_l > 64) return fail(-22, "CAGrad: at most 64 tasks");
-  int rc = cagrad_args(c, num_iterations, learning_rate, momentum);
-  if (!rc) rc = h->ensure_task_grad_buffers();
-  if (!rc) rc = h->ensure_pcgrad_buffers();
+  if (!on) return h->surgery_leave(mtsac_engine::SURGERY_CAGRAD);
+  CagradSolve s;
+  int rc = h->surgery_precheck(mtsac_engine::SURGERY_CAGRAD);
+  if (!rc) rc = cagrad_args(c, num_iterations, learning_rate, momentum, &s);
+  if (!rc) rc = h->surgery_commit(mtsac_engine::SURGERY_CAGRAD);
   if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  if (h->gexec) {  // a captured plain step is not this mode's step
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
-  if (!h->surgery) h->pc_graph_before = h->use_graph;
-  h->use_graph = false;
-  h->surgery = mtsac_engine::SURGERY_CAGRAD;
-  h->ca_c = c;
-  h->ca_iters = num_iterations;
-  h->ca_lr = learning_rate;
-  h->ca_momentum = momentum;
-  h->ca_cos = cosine_sim_logs != 0;
+  h->sg.ca = s;
+  h->sg.cosine = cosine_sim_logs != 0;
   return 0;
 }
 
 int mtsac_get_cagrad_logs(mtsac_engine* h, float* out) {
   if (!h || !out) return fail(-22, "null argument");
-  if (!h->pc_gram) return fail(-22, "CAGrad is not set up (mtsac_set_cagrad)");
-  float l[16], tw[128];
-  HIP_TRY(hipMemcpyAsync(l, h->pc_logs, sizeof(l), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(tw, h->ca_tw, sizeof(tw), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  const int T = h->T_l;
-  for (int w = 0; w < 2; ++w) {
-    for (int k = 0; k < 4; ++k) out[(4 + T) * w + k] = l[8 * w + k];
-    for (int t = 0; t < T; ++t) out[(4 + T) * w + 4 + t] = tw[64 * w + t];
-  }
-  return h->check_err();
+  if (!h->sg.gram) return fail(-22, "CAGrad is not set up (mtsac_set_cagrad)");
+  const int T = h->T_l;  // per network: the four scalars, then the task weights
+  float* scalars[2] = {out, out + 4 + T};
+  float* weights[2] = {out + 4, out + 4 + T + 4};
+  int rc = h->copy_rows(h->sg.logs, mtsac_engine::LOG_SLOT, scalars, 2, 4);
+  if (!rc) rc = h->copy_rows(h->sg.ca_tw, mtsac_engine::TS, weights, 2, T);
+  return rc ? rc : h->check_err();
 }
 
 int mtsac_task_cagrad_solve(mtsac_engine* h, int which, double c, int32_t num_iterations, double learning_rate,
@@ -3440,62 +3438,62 @@ int mtsac_task_cagrad_solve(mtsac_engine* h, int which, double c, int32_t num_it
   int rc = task_grad_ready(h, which);
   if (rc) return rc;
   if (!w || !task_weights || !logs || !obj_hist) return fail(-22, "null argument");
-  if (h->T_l > 64) return fail(-22, "CAGrad: at most 64 tasks");
-  if ((rc = cagrad_args(c, num_iterations, learning_rate, momentum))) return rc;
-  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  if (h->T_l > mtsac_engine::TS) return fail(-22, "CAGrad: at most 64 tasks");
+  CagradSolve s;
+  if ((rc = cagrad_args(c, num_iterations, learning_rate, momentum, &s))) return rc;
+  if ((rc = h->ensure_surgery_buffers())) return rc;
   const int T = h->T_l;
   HIP_TRY(hipStreamSynchronize(h->st));
-  if (w0) HIP_TRY(hipMemcpy(h->ca_w0, w0, sizeof(double) * T, hipMemcpyHostToDevice));
-  h->cur = h->st;
-  h->pc_gram_of(which);
-  h->ca_solve_of(which, c, num_iterations, learning_rate, momentum, w0 ? h->ca_w0 : nullptr, cosine_sim_logs != 0);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(w, h->pc_w + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(task_weights, h->ca_tw + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(logs, h->pc_logs + 8 * which, sizeof(float) * 6, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(obj_hist, h->ca_hist + (size_t)mtsac_engine::CA_MAX_ITERS * which,
-                         sizeof(double) * num_iterations, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
+  if (w0) HIP_TRY(hipMemcpy(h->sg.ca_w0, w0, sizeof(double) * T, hipMemcpyHostToDevice));
+  s.w0 = w0 ? h->sg.ca_w0 : nullptr;
+  s.cosine_logs = cosine_sim_logs != 0;
+  float lg[mtsac_engine::LOG_SLOT];
+  if ((rc = h->solve_alone(which, s, w, lg))) return rc;
+  std::copy(lg, lg + 6, logs);
+  HIP_TRY(hipMemcpy(task_weights, h->sg.ca_tw + mtsac_engine::TS * which, sizeof(float) * T, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(obj_hist, h->sg.ca_hist + (size_t)mtsac_engine::CA_MAX_ITERS * which,
+                    sizeof(double) * num_iterations, hipMemcpyDeviceToHost));
   return 0;
 }
 
 // ---------------------------------------------------------------- GradNorm
-static int gradnorm_args(double asymmetry, const double* lr, const double* eps, const double* max_norm, int nets) {
+// one network's arguments checked, then as the solve's parameter block (mtsac_set_gradnorm's or a kernel-alone
+// call's; the count stays 0)
+static int gradnorm_args(double asymmetry, int32_t per_task_clip, double lr, double eps, double max_norm,
+                         int32_t weighted_norms, GradnormSolve* s) {
   if (!std::isfinite(asymmetry)) return fail(-22, "GradNorm: asymmetry must be finite");
-  for (int w = 0; w < nets; ++w) {
-    if (!std::isfinite(lr[w]) || !std::isfinite(eps[w])) return fail(-22, "GradNorm: inner lr and eps must be finite");
-    if (std::isnan(max_norm[w]) || std::isinf(max_norm[w]))
-      return fail(-22, "GradNorm: inner max_grad_norm must be finite (negative: none)");
-  }
+  if (!std::isfinite(lr) || !std::isfinite(eps)) return fail(-22, "GradNorm: inner lr and eps must be finite");
+  if (std::isnan(max_norm) || std::isinf(max_norm))
+    return fail(-22, "GradNorm: inner max_grad_norm must be finite (negative: none)");
+  *s = GradnormSolve{};
+  s->asymmetry = asymmetry;
+  s->per_task_clip = per_task_clip != 0;
+  s->lr = lr;
+  s->eps = eps;
+  s->max_norm = max_norm < 0.0 ? -1.0 : max_norm;
+  s->weighted = weighted_norms != 0;
   return 0;
 }
 
 int mtsac_set_gradnorm(mtsac_engine* h, int32_t on, double asymmetry, const int32_t* per_task_clip,
                        const double* inner_lr, const double* inner_eps, const double* inner_max_grad_norm,
                        const float* initial_weights, int32_t weighted_norms) {
+  constexpr int TS = mtsac_engine::TS, ROWS = mtsac_engine::GN_ROWS;
   if (!h) return fail(-22, "null engine");
-  if (!on) {
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (h->surgery == mtsac_engine::SURGERY_GRADNORM) {
-      h->use_graph = h->pc_graph_before;
-      h->surgery = mtsac_engine::SURGERY_NONE;
-    }
-    return 0;
-  }
-  if (h->surgery == mtsac_engine::SURGERY_PCGRAD) return fail(-16, "PCGrad is on (mtsac_set_pcgrad(0) first)");
-  if (h->surgery == mtsac_engine::SURGERY_CAGRAD) return fail(-16, "CAGrad is on (mtsac_set_cagrad(0) first)");
-  if (h->T_l != h->T_g || h->sharded()) return fail(-95, "GradNorm needs every task on one engine (unsharded)");
-  if (h->cfg.use_task_weights)
-    return fail(-95, "GradNorm with use_task_weights: the reference's split losses multiply by the unsplit weights");
-  if (h->T_l > 64) return fail(-22, "GradNorm: at most 64 tasks");
-  if (!per_task_clip || !inner_lr || !inner_eps || !inner_max_grad_norm) return fail(-22, "null argument");
-  int rc = gradnorm_args(asymmetry, inner_lr, inner_eps, inner_max_grad_norm, 2);
+  if (!on) return h->surgery_leave(mtsac_engine::SURGERY_GRADNORM);
+  int rc = h->surgery_precheck(mtsac_engine::SURGERY_GRADNORM);
   if (rc) return rc;
+  if (!per_task_clip || !inner_lr || !inner_eps || !inner_max_grad_norm) return fail(-22, "null argument");
+  GradnormSolve s[2];
+  for (int w = 0; w < 2; ++w)
+    if ((rc = gradnorm_args(asymmetry, per_task_clip[w], inner_lr[w], inner_eps[w], inner_max_grad_norm[w],
+                            weighted_norms, &s[w])))
+      return rc;
   // init (gradnorm.py:70-84): the weights normalised to sum T in fp32, the first losses +inf, Adam zeros
   const int T = h->T_l;
-  std::vector<float> stt(2 * 4 * 64, 0.f);
+  std::vector<float> stt(2 * ROWS * TS, 0.f);
   for (int w = 0; w < 2; ++w) {
-    float* tw = stt.data() + 4 * 64 * w;
+    float* tw = stt.data() + ROWS * TS * w;
     float sum = 0.f;
     for (int t = 0; t < T; ++t) {
       tw[t] = initial_weights ? initial_weights[w * T + t] : 1.f;
@@ -3505,39 +3503,21 @@ int mtsac_set_gradnorm(mtsac_engine* h, int32_t on, double asymmetry, const int3
     if (sum == 0.f || !std::isfinite(sum)) return fail(-22, "GradNorm: initial_weights sum to zero");
     for (int t = 0; t < T; ++t) {
       tw[t] = (tw[t] / sum) * (float)T;
-      tw[64 + t] = INFINITY;
+      tw[TS + t] = INFINITY;
     }
   }
-  if ((rc = h->ensure_task_grad_buffers())) return rc;
-  if ((rc = h->ensure_pcgrad_buffers())) return rc;
-  HIP_TRY(hipStreamSynchronize(h->st));
-  if (h->gexec) {  // a captured plain step is not this mode's step
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
-  HIP_TRY(hipMemcpy(h->gn_state, stt.data(), sizeof(float) * stt.size(), hipMemcpyHostToDevice));
-  if (!h->surgery) h->pc_graph_before = h->use_graph;
-  h->use_graph = false;
-  h->surgery = mtsac_engine::SURGERY_GRADNORM;
-  h->gn_asym = asymmetry;
-  h->gn_weighted = weighted_norms != 0;
-  h->gn_ready = true;
-  for (int w = 0; w < 2; ++w) {
-    h->gn_clip[w] = per_task_clip[w] != 0;
-    h->gn_lr[w] = inner_lr[w];
-    h->gn_eps[w] = inner_eps[w];
-    h->gn_max_norm[w] = inner_max_grad_norm[w] < 0.0 ? -1.0 : inner_max_grad_norm[w];
-    h->gn_count[w] = 0;
-  }
+  if ((rc = h->surgery_commit(mtsac_engine::SURGERY_GRADNORM))) return rc;
+  HIP_TRY(hipMemcpy(h->sg.gn_state, stt.data(), sizeof(float) * stt.size(), hipMemcpyHostToDevice));
+  h->sg.gn[0] = s[0];
+  h->sg.gn[1] = s[1];
+  h->sg.gn_ready = true;
   return 0;
 }
 
 static int gradnorm_slot(mtsac_engine* h, int which) {
   if (!h) return fail(-22, "null engine");
   if (which != 0 && which != 1) return fail(-22, "which: 0 critic, 1 actor");
-  if (!h->gn_ready) return fail(-22, "GradNorm is not set up (mtsac_set_gradnorm)");
+  if (!h->sg.gn_ready) return fail(-22, "GradNorm is not set up (mtsac_set_gradnorm)");
   return 0;
 }
 
@@ -3545,13 +3525,9 @@ int mtsac_gradnorm_get_state(mtsac_engine* h, int which, float* task_weights, fl
                              float* nu, int64_t* count) {
   if (int rc = gradnorm_slot(h, which)) return rc;
   if (!task_weights || !original_losses || !mu || !nu || !count) return fail(-22, "null argument");
-  float stt[4 * 64];
-  HIP_TRY(hipMemcpyAsync(stt, h->gn_state + 4 * 64 * which, sizeof(stt), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  float* outs[4] = {task_weights, original_losses, mu, nu};
-  for (int k = 0; k < 4; ++k)
-    for (int t = 0; t < h->T_l; ++t) outs[k][t] = stt[64 * k + t];
-  *count = h->gn_count[which];
+  float* rows[4] = {task_weights, original_losses, mu, nu};
+  if (int rc = h->copy_rows(h->sg.gn_state_of(which), mtsac_engine::TS, rows, 4, h->T_l)) return rc;
+  *count = h->sg.gn[which].count;
   return h->check_err();
 }
 
@@ -3559,43 +3535,31 @@ int mtsac_gradnorm_set_state(mtsac_engine* h, int which, const float* task_weigh
                              const float* mu, const float* nu, int64_t count) {
   if (int rc = gradnorm_slot(h, which)) return rc;
   if (!task_weights || !original_losses || !mu || !nu || count < 0) return fail(-22, "bad argument");
-  float stt[4 * 64] = {};
-  const float* ins[4] = {task_weights, original_losses, mu, nu};
-  for (int k = 0; k < 4; ++k)
-    for (int t = 0; t < h->T_l; ++t) stt[64 * k + t] = ins[k][t];
-  HIP_TRY(hipStreamSynchronize(h->st));
-  HIP_TRY(hipMemcpy(h->gn_state + 4 * 64 * which, stt, sizeof(stt), hipMemcpyHostToDevice));
-  h->gn_count[which] = count;
+  float* rows[4] = {const_cast<float*>(task_weights), const_cast<float*>(original_losses), const_cast<float*>(mu),
+                    const_cast<float*>(nu)};
+  if (int rc = h->copy_rows(h->sg.gn_state_of(which), mtsac_engine::TS, rows, 4, h->T_l, true)) return rc;
+  h->sg.gn[which].count = count;
   return 0;
 }
 
 int mtsac_get_gradnorm_logs(mtsac_engine* h, float* out) {
   if (int rc = gradnorm_slot(h, 0)) return rc;
   if (!out) return fail(-22, "null argument");
-  float l[16], stt[2 * 4 * 64];
-  HIP_TRY(hipMemcpyAsync(l, h->pc_logs, sizeof(l), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(stt, h->gn_state, sizeof(stt), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  const int T = h->T_l;
+  const int T = h->T_l, per_net = 2 * T + 1;  // task_weights, original_losses, gradnorm_loss
   for (int w = 0; w < 2; ++w) {
-    float* o = out + (2 * T + 1) * w;
-    for (int t = 0; t < T; ++t) {
-      o[t] = stt[4 * 64 * w + t];
-      o[T + t] = stt[4 * 64 * w + 64 + t];
-    }
-    o[2 * T] = l[8 * w];
+    float* rows[2] = {out + per_net * w, out + per_net * w + T};
+    if (int rc = h->copy_rows(h->sg.gn_state_of(w), mtsac_engine::TS, rows, 2, T)) return rc;
   }
+  float* loss[2] = {out + 2 * T, out + per_net + 2 * T};
+  if (int rc = h->copy_rows(h->sg.logs, mtsac_engine::LOG_SLOT, loss, 2, 1)) return rc;
   return h->check_err();
 }
 
 int mtsac_get_gradnorm_task_losses(mtsac_engine* h, float* out) {
   if (int rc = gradnorm_slot(h, 0)) return rc;
   if (!out) return fail(-22, "null argument");
-  float l[2 * 64];
-  HIP_TRY(hipMemcpyAsync(l, h->gn_loss, sizeof(l), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  for (int w = 0; w < 2; ++w)
-    for (int t = 0; t < h->T_l; ++t) out[h->T_l * w + t] = l[64 * w + t];
+  float* rows[2] = {out, out + h->T_l};
+  if (int rc = h->copy_rows(h->sg.gn_loss, mtsac_engine::TS, rows, 2, h->T_l)) return rc;
   return h->check_err();
 }
 
@@ -3603,35 +3567,26 @@ int mtsac_task_gradnorm_solve(mtsac_engine* h, int which, const float* task_loss
                               int32_t per_task_clip, double inner_lr, double inner_eps, double inner_max_grad_norm,
                               int32_t weighted_norms, float* task_weights, float* original_losses, float* mu,
                               float* nu, int64_t* count, float* w, float* logs) {
+  constexpr int TS = mtsac_engine::TS, ALONE = mtsac_engine::GN_ALONE;
   int rc = task_grad_ready(h, which);
   if (rc) return rc;
   if (!task_losses || !task_weights || !original_losses || !mu || !nu || !count || !w || !logs)
     return fail(-22, "null argument");
-  if (h->T_l > 64) return fail(-22, "GradNorm: at most 64 tasks");
+  if (h->T_l > TS) return fail(-22, "GradNorm: at most 64 tasks");
   if (*count < 0) return fail(-22, "GradNorm: negative count");
-  if ((rc = gradnorm_args(asymmetry, &inner_lr, &inner_eps, &inner_max_grad_norm, 1))) return rc;
-  if ((rc = h->ensure_pcgrad_buffers())) return rc;
+  GradnormSolve s;
+  if ((rc = gradnorm_args(asymmetry, per_task_clip, inner_lr, inner_eps, inner_max_grad_norm, weighted_norms, &s)))
+    return rc;
+  if ((rc = h->ensure_surgery_buffers())) return rc;
+  s.count = *count + 1;
   const int T = h->T_l;
-  float stt[4 * 64] = {}, ls[64] = {};
   float* io[4] = {task_weights, original_losses, mu, nu};
-  for (int k = 0; k < 4; ++k)
-    for (int t = 0; t < T; ++t) stt[64 * k + t] = io[k][t];
-  for (int t = 0; t < T; ++t) ls[t] = task_losses[t];
-  HIP_TRY(hipStreamSynchronize(h->st));
-  HIP_TRY(hipMemcpy(h->gn_state + 4 * 64 * 2, stt, sizeof(stt), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->gn_loss + 64 * 2, ls, sizeof(ls), hipMemcpyHostToDevice));
-  h->cur = h->st;
-  h->pc_gram_of(which);
-  h->gn_solve_of(which, 2, asymmetry, per_task_clip != 0, inner_lr, inner_eps,
-                 inner_max_grad_norm < 0.0 ? -1.0 : inner_max_grad_norm, weighted_norms != 0, *count + 1);
-  HIP_TRY(hipGetLastError());
-  float lg[8];
-  HIP_TRY(hipMemcpyAsync(stt, h->gn_state + 4 * 64 * 2, sizeof(stt), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(w, h->pc_w + 64 * which, sizeof(float) * T, hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipMemcpyAsync(lg, h->pc_logs + 8 * which, sizeof(lg), hipMemcpyDeviceToHost, h->st));
-  HIP_TRY(hipStreamSynchronize(h->st));
-  for (int k = 0; k < 4; ++k)
-    for (int t = 0; t < T; ++t) io[k][t] = stt[64 * k + t];
+  float* ls[1] = {const_cast<float*>(task_losses)};
+  float lg[mtsac_engine::LOG_SLOT];
+  if ((rc = h->copy_rows(h->sg.gn_state_of(ALONE), TS, io, 4, T, true)) ||
+      (rc = h->copy_rows(h->sg.gn_loss_of(ALONE), TS, ls, 1, T, true)) ||
+      (rc = h->solve_alone(which, s, w, lg, ALONE)) || (rc = h->copy_rows(h->sg.gn_state_of(ALONE), TS, io, 4, T)))
+    return rc;
   *count += 1;
   logs[0] = lg[0];
   logs[1] = lg[1];
@@ -3643,7 +3598,7 @@ int mtsac_update_many(mtsac_engine* h, int32_t steps) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
   if (steps <= 0) return 0;
-  if (h->surgery) {  // eager, one stream, no overlap between steps; PCGrad's task orders are drawn on the device
+  if (h->sg.kind) {  // eager, one stream, no overlap between steps; PCGrad's task orders are drawn on the device
     if (h->sharded()) return fail(-95, "PCGrad / CAGrad / GradNorm needs every task on one engine (unsharded)");
     h->tl_next = 0;
     for (int s = 0; s < steps; ++s) h->pcgrad_step(true, true);
@@ -3659,12 +3614,7 @@ int mtsac_update_many(mtsac_engine* h, int32_t steps) {
     HIP_TRY(hipGetLastError());
     return 0;
   }
-  if (h->gexec && h->graph_timed != h->timing) {
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
+  if (h->gexec && h->graph_timed != h->timing) h->drop_graph();
   if (!h->gexec) {
     h->tl_next = 0;
     HIP_TRY(hipGraphCreate(&h->graph, 0));
@@ -3692,7 +3642,7 @@ int mtsac_get_logs(mtsac_engine* h, float* logs) {
 
 int mtsac_enable_graph(mtsac_engine* h, int32_t enable) {
   if (!h) return fail(-22, "null engine");
-  if (enable && h->surgery)
+  if (enable && h->sg.kind)
     return fail(-95, "the PCGrad / CAGrad / GradNorm step is not captured: graph replay is unavailable in this mode");
   h->use_graph = enable != 0;
   return 0;
@@ -3817,12 +3767,7 @@ int mtsac_comm_init_timeout(mtsac_engine* h, const void* unique_id, int32_t nran
   h->comm = comm;
   h->nranks = nranks;
   h->rank = rank;
-  if (h->gexec) {
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
+  h->drop_graph();  // the captured step has no collectives
   return 0;
 }
 
@@ -3843,12 +3788,7 @@ int mtsac_set_noise_state(mtsac_engine* h, uint64_t seed, uint64_t counter) {
   HIP_TRY(hipMemcpy(h->counter, &c, sizeof(c), hipMemcpyHostToDevice));
   if (seed != h->cfg.noise_seed) {  // the seed is a kernel argument inside the step graph
     h->cfg.noise_seed = seed;
-    if (h->gexec) {
-      (void)hipGraphExecDestroy(h->gexec);
-      (void)hipGraphDestroy(h->graph);
-      h->gexec = nullptr;
-      h->graph = nullptr;
-    }
+    h->drop_graph();
   }
   return 0;
 }
@@ -3889,12 +3829,7 @@ int mtsac_set_sharded_optimizer(mtsac_engine* h, int32_t on) {
   if (want == h->zero_req) return 0;
   HIP_TRY(hipStreamSynchronize(h->st));
   h->zero_req = want;
-  if (h->gexec) {  // the captured step holds the other optimizer form (bucket ops, optimize_zero)
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
+  h->drop_graph();  // the captured step holds the other optimizer form (bucket ops, optimize_zero)
   return 0;
 }
 
@@ -3966,12 +3901,7 @@ int mtsac_debug_set_collective_model(mtsac_engine* h, int32_t nranks, double bus
       h->cm_cap = need;
     }
   }
-  if (h->gexec) {  // the step's structure changed (buckets, sharded reductions)
-    (void)hipGraphExecDestroy(h->gexec);
-    (void)hipGraphDestroy(h->graph);
-    h->gexec = nullptr;
-    h->graph = nullptr;
-  }
+  h->drop_graph();  // the step's structure changed (buckets, sharded reductions)
   return 0;
 }
 

@@ -14,15 +14,10 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "wave_sum.h"
 
 namespace mtsac {
 namespace {
-
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __device__ inline float wave_sum_f(float v) {
 #pragma unroll

@@ -21,6 +21,7 @@
 
 #include "devrng.h"
 #include "kernels.h"
+#include "wave_sum.h"
 
 namespace mtsac {
 namespace {
@@ -147,12 +148,6 @@ __global__ __launch_bounds__(256) void gram_sum_kernel(const double* __restrict_
 }
 
 // ------------------------------------------------------------------ solve
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // One wavefront; lane i owns row i of C and D (in the drawn order: row i is task perm[i]).
 __global__ __launch_bounds__(64) void pcgrad_solve_kernel(PcgradSolve s) {
   __shared__ double D[TP][TP];  // [k][i]

@@ -14,17 +14,14 @@ import numpy as np
 
 from . import _lib
 from ._lib import LOG_KEYS, Batch, Config, MTSACError, check
-
 # PCGradState fields (mtrl/optim/pcgrad.py:12-17), the order of mtsac_get_pcgrad_logs per network
-PCGRAD_LOG_KEYS = ("n_grad_conflicts", "avg_grad_magnitude", "avg_grad_magnitude_before_surgery",
-                   "avg_cosine_similarity", "avg_cosine_similarity_diff")
+from .pcgrad import LOG_KEYS as PCGRAD_LOG_KEYS
 # CAGradState fields (mtrl/optim/cagrad.py:12-17); mtsac_get_cagrad_logs holds the four scalars, then
 # task_weights
-CAGRAD_LOG_KEYS = ("task_weights", "avg_grad_magnitude", "avg_grad_magnitude_before_surgery",
-                   "avg_cosine_similarity", "cagrad_objective")
+from .cagrad import LOG_KEYS as CAGRAD_LOG_KEYS
 # GradNormState fields the reference logs (mtrl/optim/gradnorm.py:34-37, mtsac.py:1224-1239): arrays of
 # length T; the inner opt_state lives in the checkpoint, not in the logs
-GRADNORM_LOG_KEYS = ("task_weights", "original_losses")
+from .gradnorm import LOG_KEYS as GRADNORM_LOG_KEYS
 
 
 def _ptr(x) -> tuple[int, Any]:
