@@ -103,7 +103,7 @@ typedef struct mtsac_config {
   int32_t task_begin;       /* first task owned by this engine (sharding)      */
   int32_t task_count;       /* tasks owned by this engine (= T unsharded)      */
   int32_t obs_dim;          /* observation width incl. one-hot (39 + T)        */
-  int32_t action_dim;       /* A (4)                                           */
+  int32_t action_dim;       /* A (4); 1 .. 64 (A > 4: the wide head kernels)    */
   int32_t actor_width, actor_depth;
   int32_t critic_width, critic_depth;
   int32_t num_critics;      /* ensemble size (2)                               */

@@ -141,7 +141,9 @@ int mtsac_debug_head_bwd_split(int mode);
  * (h, eps and every output then hold two sets, [2][...]).  h [B][W], Wh [T_l][W][2A], bh [T_l][2A],
  * eps [B][A] (injected noise, required).  flags bit 0: with WhT from head_transpose; bit 1 / bit 2: the
  * action planes as split3 / split2h (at exponent 14), returned in planes [B][ld_a] as their unscaled sum.
- * a_out, a_out2 [B][ld_a] (ld_a >= A: the columns past A stay NaN), logpi [B], cache [B][5A]. */
+ * a_out, a_out2 [B][ld_a] (ld_a >= A: the columns past A stay NaN), logpi [B], cache [B][5A].  A <= 64; a wide
+ * head (A > 4) needs W % 4 == 0.  The output buffers of a call (here and in the head backward and action grad
+ * below) must be distinct: each is copied back in turn, so two that share an address are refused (-22). */
 int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
                             const float* Wh, const float* bh, const float* eps, float ls_min, float ls_max,
                             float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,

@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -156,6 +157,14 @@ bool tasks_ok(const int* task, int B, int T_l) {
   if (!task || B < 1 || T_l < 1 || T_l > 64) return false;
   for (int b = 0; b < B; ++b)
     if (task[b] < 0 || task[b] >= T_l) return false;
+  return true;
+}
+// host output buffers of one call must not share a start address: each is copied back over whatever the
+// one before it left there, so the caller would read one output under another's name (null entries skipped)
+bool outputs_distinct(std::initializer_list<const void*> outs) {
+  for (auto a = outs.begin(); a != outs.end(); ++a)
+    for (auto b = a + 1; b != outs.end(); ++b)
+      if (*a != nullptr && *a == *b) return false;
   return true;
 }
 TaskLists make_lists(Guarded& g, const int* task, int B, int T_l) {
@@ -914,9 +923,10 @@ int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, i
                             float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,
                             int* rows) {
   const bool whT = flags & 1, p3 = flags & 2, p2h = flags & 4;
-  if (form < 0 || form > 2 || (flags & ~7) || (p3 && p2h) || W < 1 || A < 1 || A > 4 || ld_a < A || !h || !Wh || !bh ||
+  if (form < 0 || form > 2 || (flags & ~7) || (p3 && p2h) || W < 1 || A < 1 || A > 64 || !head_kernels_cover(2 * A, W) || ld_a < A || !h || !Wh || !bh ||
       !eps || !a_out || !a_out2 || !logpi || !cache || !counts || !rows || ((p3 || p2h) && !planes) ||
-      !tasks_ok(task, B, T_l) || (long long)B * W >= (1LL << 28))
+      !tasks_ok(task, B, T_l) || (long long)B * W >= (1LL << 28) ||
+      !outputs_distinct({a_out, a_out2, logpi, cache, planes, counts, rows}))
     return -22;
   if (hipSetDevice(0) != hipSuccess) return -5;
   const int hd = 2 * A, ns = form == 2 ? 2 : 1, H2E = 14;  // |a| <= 1 at 2^14 fits fp16
@@ -953,8 +963,7 @@ int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, i
     }
     pp[s] = p;
   }
-  if (form == 2) policy_head_pair(pp[0], pp[1], nullptr);
-  else policy_head(pp[0], nullptr);
+  if (!(form == 2 ? policy_head_pair(pp[0], pp[1], nullptr) : policy_head(pp[0], nullptr))) return -22;
   int rc = 0;
   if ((rc = sync_rc("policy_head")) || (rc = g.check())) return rc;
   for (int s = 0; s < ns; ++s) {
@@ -1038,10 +1047,11 @@ int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W,
                               const float* Wh, const float* dout, const float* dq, float* dz, float* dbp, float* db,
                               float* planes, float* dWh, float* dbh, int* counts, int* rows, int* info) {
   const bool p3 = flags & 1, p2h = flags & 2, compact = form == 2;
-  const bool hd_ok = hd == 1 || hd == 2 || hd == 4 || hd == 6 || hd == 8;
+  const bool hd_ok = head_kernels_cover(hd, W);  // hd 3, 5, 7 and a wide head at W % 4 != 0 have no kernel
   if (form < 0 || form > 2 || (flags & ~3) || (p3 && p2h) || !hd_ok || E < 1 || E > 4 || W < 1 || !h || !Wh || !dout ||
       !dz || !dbp || !db || !planes || !dWh || !dbh || !counts || !rows || !info || !tasks_ok(task, B, T_l) ||
-      (compact && (hd != 1 || W % 4 != 0 || !dq || !(p3 || p2h))) || (long long)E * B * W >= (1LL << 28))
+      (compact && (hd != 1 || W % 4 != 0 || !dq || !(p3 || p2h))) || (long long)E * B * W >= (1LL << 28) ||
+      !outputs_distinct({dz, dbp, db, planes, dWh, dbh, counts, rows, info}))
     return -22;
   if (hipSetDevice(0) != hipSuccess) return -5;
   const int chunks = head_backward_chunks(T_l);
@@ -1122,9 +1132,9 @@ int mtsac_debug_head_action_grad(int B, int E, int Wc, int Ic, int A, const floa
                                  const float* cache, const float* alpha_w, const float* a_data, int ld_a_data,
                                  float explore_scale, float ls_min, float ls_max, const float* row_loss_in, float* dout,
                                  float* row_loss, float* row_explore, float* dout_amax, int* dout_parts) {
-  if (B < 1 || E < 1 || E > 4 || Wc < 1 || A < 1 || A > 4 || Ic < A || !dz1 || !W0 || !cache || !alpha_w || !dout ||
+  if (B < 1 || E < 1 || E > 4 || Wc < 1 || A < 1 || A > 64 || (A > 8 && Wc % 4 != 0) || Ic < A || !dz1 || !W0 || !cache || !alpha_w || !dout ||
       !row_loss || !row_explore || !dout_amax || !dout_parts || (a_data && (ld_a_data < A || !row_loss_in)) ||
-      (long long)E * B * Wc >= (1LL << 28))
+      (long long)E * B * Wc >= (1LL << 28) || !outputs_distinct({dout, row_loss, row_explore, dout_amax, dout_parts}))
     return -22;
   if (hipSetDevice(0) != hipSuccess) return -5;
   const size_t nz = (size_t)E * B * Wc;
@@ -1165,7 +1175,7 @@ int mtsac_debug_head_action_grad(int B, int E, int Wc, int Ic, int A, const floa
   p.row_explore = g.out<float>((size_t)B, "row_explore");
   if (!g.ok) return -12;
   if (a_data && hipMemcpy(p.row_loss, row_loss_in, sizeof(float) * B, hipMemcpyHostToDevice) != hipSuccess) return -5;
-  action_grad(p, nullptr);
+  if (!action_grad(p, nullptr)) return -22;
   int rc = 0;
   if ((rc = sync_rc("action_grad")) || (rc = g.check())) return rc;
   *dout_parts = parts;

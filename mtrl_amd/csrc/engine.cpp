@@ -2473,10 +2473,13 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
     return fail(-22, "invalid task range");
   if (c.task_count > 64) return fail(-22, "at most 64 tasks per engine");
   if (c.num_tasks > EXTRA - 8) return fail(-22, "num_tasks too large");
-  if (c.action_dim < 1 || c.action_dim > 4) return fail(-22, "action_dim must be in [1, 4]");
+  if (c.action_dim < 1 || c.action_dim > 64) return fail(-22, "action_dim must be in [1, 64]");
   if (c.obs_dim < c.num_tasks) return fail(-22, "obs_dim must include the one-hot task id");
   if (c.actor_width % 4 || c.critic_width % 4 || c.actor_width <= 0 || c.critic_width <= 0)
     return fail(-22, "network widths must be positive multiples of 4");
+  // the head launch wrappers launch nothing for a head without a kernel: refuse such a network here
+  if (!head_kernels_cover(2 * c.action_dim, c.actor_width) || !head_kernels_cover(1, c.critic_width))
+    return fail(-22, "no head kernel for this action_dim / width");
   if (c.actor_depth < 1 || c.actor_depth > MAXD || c.critic_depth < 1 || c.critic_depth > MAXD)
     return fail(-22, "depth must be in [1, 8]");
   if (c.num_critics < 1 || c.num_critics > 4) return fail(-22, "num_critics must be in [1, 4]");

@@ -1115,7 +1115,14 @@ __global__ __launch_bounds__(256) void head_transpose_kernel(const float* __rest
   WhT[i] = Wh[t * per + (long long)w * hd + o];
 }
 
+#include "heads_wide.h"
+
 }  // namespace
+
+bool head_kernels_cover(int hd, int W) {
+  if (hd == 1 || hd == 2 || hd == 4 || hd == 6 || hd == 8) return W >= 1;
+  return hd > 8 && hd % 2 == 0 && hd <= WIDE_MAX_HD && W >= 4 && W % 4 == 0;  // the wide family (heads_wide.h): hd = 2 A
+}
 
 void head_transpose(const float* Wh, int T_l, int W, int hd, float* WhT, hipStream_t st) {
   const long long n = (long long)T_l * W * hd;
@@ -1123,8 +1130,21 @@ void head_transpose(const float* Wh, int T_l, int W, int hd, float* WhT, hipStre
   hipLaunchKernelGGL(head_transpose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, Wh, W, hd, n, WhT);
 }
 
-void policy_head(const PolicyParams& p, hipStream_t st) {
+bool policy_head(const PolicyParams& p, hipStream_t st) {
   const int hd = p.head.hd;
+  if (!head_kernels_cover(hd, p.head.W) || hd != 2 * p.A) return false;  // no kernel for this head: not launched
+  if (hd > 8) {  // the wide family: a workgroup per 16-row tile of a task's list, or per row (rollout)
+    const int nt = wide_nt(hd);
+    if (p.counts != nullptr) {
+      PolicyPair pp{};
+      pp.p[0] = p;
+      const dim3 grid((unsigned)p.T_l, (unsigned)((p.max_count + 15) / 16), 1);
+      WIDE_NT_LAUNCH(nt, policy_head_wide_kernel, grid, dim3(64 * WIDE_KS), st, pp);
+    } else if (p.head.B > 0) {
+      WIDE_NT_LAUNCH(nt, policy_head_wide_row_kernel, dim3((unsigned)p.head.B), dim3(64 * WIDE_KS), st, p);
+    }
+    return true;
+  }
   if (p.counts != nullptr) {
     const int rw = rows_per_wave((long long)p.T_l * ((p.max_count + 3) / 4));
     dim3 grid((unsigned)p.T_l, (unsigned)((p.max_count + 4 * rw - 1) / (4 * rw)));
@@ -1135,9 +1155,9 @@ void policy_head(const PolicyParams& p, hipStream_t st) {
     if (hd == 8) { PHG(8) }
     else if (hd == 6) { PHG(6) }
     else if (hd == 4) { PHG(4) }
-    else { PHG(2) }
+    else { PHG(2) }  // hd == 2 (head_kernels_cover)
 #undef PHG
-    return;
+    return true;
   }
   dim3 grid((p.head.B + 3) / 4);
   if (hd == 8)
@@ -1146,15 +1166,26 @@ void policy_head(const PolicyParams& p, hipStream_t st) {
     hipLaunchKernelGGL(policy_head_kernel<6>, grid, dim3(256), 0, st, p);
   else if (hd == 4)
     hipLaunchKernelGGL(policy_head_kernel<4>, grid, dim3(256), 0, st, p);
-  else
+  else  // hd == 2 (head_kernels_cover)
     hipLaunchKernelGGL(policy_head_kernel<2>, grid, dim3(256), 0, st, p);
+  return true;
 }
 
-void policy_head_pair(const PolicyParams& a, const PolicyParams& b, hipStream_t st) {
+bool policy_head_pair(const PolicyParams& a, const PolicyParams& b, hipStream_t st) {
   if (!a.counts || !b.counts || a.head.hd != b.head.hd || a.T_l != b.T_l || a.max_count != b.max_count) {
-    policy_head(a, st);
-    policy_head(b, st);
-    return;
+    const bool ra = policy_head(a, st), rb = policy_head(b, st);
+    return ra && rb;
+  }
+  if (!head_kernels_cover(a.head.hd, a.head.W) || a.head.hd != 2 * a.A || b.head.hd != 2 * b.A ||
+      !head_kernels_cover(b.head.hd, b.head.W))
+    return false;
+  if (a.head.hd > 8) {  // the wide family: the same kernel as the grouped form, blockIdx.z picks the head
+    PolicyPair pw{};
+    pw.p[0] = a;
+    pw.p[1] = b;
+    const dim3 gridw((unsigned)a.T_l, (unsigned)((a.max_count + 15) / 16), 2);
+    WIDE_NT_LAUNCH(wide_nt(a.head.hd), policy_head_wide_kernel, gridw, dim3(64 * WIDE_KS), st, pw);
+    return true;
   }
   const int rw = rows_per_wave(2LL * a.T_l * ((a.max_count + 3) / 4));
   const dim3 grid((unsigned)a.T_l, (unsigned)((a.max_count + 4 * rw - 1) / (4 * rw)), 2);
@@ -1168,8 +1199,9 @@ void policy_head_pair(const PolicyParams& a, const PolicyParams& b, hipStream_t 
   if (a.head.hd == 8) { PHP(8) }
   else if (a.head.hd == 6) { PHP(6) }
   else if (a.head.hd == 4) { PHP(4) }
-  else { PHP(2) }
+  else { PHP(2) }  // hd == 2 (head_kernels_cover)
 #undef PHP
+  return true;
 }
 
 void critic_head(const CriticHeadParams& p, hipStream_t st) {
@@ -1184,14 +1216,21 @@ void active_rows(const float* dq, int E, int B, int* n, int* rows, int* slot, hi
   hipLaunchKernelGGL(active_rows_kernel, dim3((unsigned)E), dim3(1024), 0, st, dq, B, n, rows, slot);
 }
 
-void head_backward_data(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
+bool head_backward_data(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
                         const int* rows, int max_rows, int T_l, hipStream_t st, PlaneOut po, float* dbp,
                         const int* slot) {
+  if (!head_kernels_cover(hp.hd, hp.W) || (slot != nullptr && hp.hd != 1)) return false;  // not launched
+  if (hp.hd > 8) {  // the wide family: a workgroup per (16 columns, task, member), a wave per row slice
+    const dim3 gridw((unsigned)((hp.W + 15) / 16), (unsigned)T_l, (unsigned)hp.E);
+    hipLaunchKernelGGL(head_bwd_data_wide_kernel, gridw, dim3(256), 0, st, hp, dout, s_dout, dz, po, dbp, counts, rows,
+                       max_rows);
+    return true;
+  }
   const dim3 grid((unsigned)((hp.W + 255) / 256), (unsigned)(T_l * HB_RS), (unsigned)hp.E);
   if (slot != nullptr) {  // hd = 1 (the critic), planes only: the caller's conditions
     hipLaunchKernelGGL(head_bwd_data_compact_kernel<1>, grid, dim3(256), 0, st, hp, dout, s_dout, po, counts, rows,
                        max_rows, slot);
-    return;
+    return true;
   }
 #define HBD_LAUNCH(HDV)                                                                                  \
   hipLaunchKernelGGL(head_bwd_data_kernel<HDV>, grid, dim3(256), 0, st, hp, dout, s_dout, dz, po, dbp, counts, \
@@ -1201,17 +1240,31 @@ void head_backward_data(const HeadParams& hp, const float* dout, long long s_dou
     case 2: HBD_LAUNCH(2); break;
     case 4: HBD_LAUNCH(4); break;
     case 6: HBD_LAUNCH(6); break;
-    default: HBD_LAUNCH(8); break;
+    case 8: HBD_LAUNCH(8); break;
+    default: return false;  // (head_kernels_cover)
   }
 #undef HBD_LAUNCH
+  return true;
 }
 
 int head_backward_chunks(int T_l) { return T_l * HB_RS; }
 
+static void head_backward_weight_wide(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
+                                      const int* rows, int max_rows, int T_l, float* dWh, float* dbh, hipStream_t st) {
+  const dim3 grid((unsigned)T_l, (unsigned)((hp.W + 63) / 64), (unsigned)hp.E);
+  WIDE_NT_LAUNCH(wide_nt(hp.hd), head_bwd_weight_wide_kernel, grid, dim3(256), st, hp, dout, s_dout, counts, rows,
+                 max_rows, dWh, dbh);
+}
+
 bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
                         const int* rows, int max_rows, int T_l, PlaneOut po, float* dbp, float* dWh, float* dbh,
                         hipStream_t st) {
-  if (hp.W % 4 != 0) return false;  // the scalar weight kernel: two launches
+  if (hp.W % 4 != 0 || !head_kernels_cover(hp.hd, hp.W)) return false;  // the scalar weight kernel: two launches
+  if (hp.hd > 8) {  // the wide family has no one-launch form: its two kernels, one after the other
+    head_backward_data(hp, dout, s_dout, dz, counts, rows, max_rows, T_l, st, po, dbp);
+    head_backward_weight_wide(hp, dout, s_dout, counts, rows, max_rows, T_l, dWh, dbh, st);
+    return true;
+  }
   const int gw = (hp.W + 255) / 256;
   static const bool split_req = [] {  // MTSAC_HEAD_BWD_SPLIT=1: the data and weight passes as separate blocks
     const char* e = getenv("MTSAC_HEAD_BWD_SPLIT");
@@ -1235,15 +1288,21 @@ bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dou
     case 2: HBB_LAUNCH(2); break;
     case 4: HBB_LAUNCH(4); break;
     case 6: HBB_LAUNCH(6); break;
-    default: HBB_LAUNCH(8); break;
+    case 8: HBB_LAUNCH(8); break;
+    default: return false;  // (head_kernels_cover)
   }
 #undef HBB_LAUNCH
   return true;
 }
 
-void head_backward_weight(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
+bool head_backward_weight(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
                           const int* rows, int max_rows, float* dWh, float* dbh, hipStream_t st) {
+  if (!head_kernels_cover(hp.hd, hp.W)) return false;  // not launched
   const unsigned T_l = (unsigned)(hp.sbh / hp.hd);  // bias stride per member = T_l * hd
+  if (hp.hd > 8) {
+    head_backward_weight_wide(hp, dout, s_dout, counts, rows, max_rows, (int)T_l, dWh, dbh, st);
+    return true;
+  }
 #define HBW_LAUNCH(K, HDV, WPB)                                                                             \
   hipLaunchKernelGGL(K<HDV>, dim3(T_l, (hp.W + WPB - 1) / WPB, hp.E), dim3(256), 0, st, hp, dout, s_dout, counts, \
                      rows, max_rows, dWh, dbh)
@@ -1253,9 +1312,11 @@ void head_backward_weight(const HeadParams& hp, const float* dout, long long s_d
     case 2: if (vec) HBW_LAUNCH(head_bwd_weight_kernel, 2, 256); else HBW_LAUNCH(head_bwd_weight_scalar_kernel, 2, 64); break;
     case 4: if (vec) HBW_LAUNCH(head_bwd_weight_kernel, 4, 256); else HBW_LAUNCH(head_bwd_weight_scalar_kernel, 4, 64); break;
     case 6: if (vec) HBW_LAUNCH(head_bwd_weight_kernel, 6, 256); else HBW_LAUNCH(head_bwd_weight_scalar_kernel, 6, 64); break;
-    default: if (vec) HBW_LAUNCH(head_bwd_weight_kernel, 8, 256); else HBW_LAUNCH(head_bwd_weight_scalar_kernel, 8, 64); break;
+    case 8: if (vec) HBW_LAUNCH(head_bwd_weight_kernel, 8, 256); else HBW_LAUNCH(head_bwd_weight_scalar_kernel, 8, 64); break;
+    default: return false;  // (head_kernels_cover)
   }
 #undef HBW_LAUNCH
+  return true;
 }
 
 void head_backward_weight_inject(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
@@ -1265,7 +1326,16 @@ void head_backward_weight_inject(const HeadParams& hp, const float* dout, long l
                      dim3(256), 0, st, hp, dout, s_dout, counts, rows, max_rows, dWh, dbh);
 }
 
-void action_grad(const ActionGradParams& p, hipStream_t st) {
+// A <= 8 keeps action_grad_kernel (A = 4: its AM = 4 instance, else AM = 8, which holds any A <= 8 in
+// registers); A > 8 takes the wide kernel (Wc % 4 == 0)
+bool action_grad(const ActionGradParams& p, hipStream_t st) {
+  if (p.A < 1 || p.A > WIDE_MAX_HD / 2 || (p.A > 8 && p.Wc % 4 != 0)) return false;  // not launched
+  if (p.A > 8) {
+    const dim3 gridw((unsigned)std::min((p.B + 15) / 16, PLANE_REC_PARTS));
+    if (p.dout_parts) *p.dout_parts = (int)gridw.x;  // one partial max per workgroup
+    WIDE_NT_LAUNCH(wide_nt(p.A), action_grad_wide_kernel, gridw, dim3(64 * WIDE_KS), st, p);
+    return true;
+  }
   const int rw = rows_per_wave((p.B + 3) / 4);
   const dim3 grid((unsigned)std::min((p.B + 4 * rw - 1) / (4 * rw), PLANE_REC_PARTS));
   if (p.dout_parts) *p.dout_parts = (int)grid.x;  // one partial max per workgroup
@@ -1276,6 +1346,7 @@ void action_grad(const ActionGradParams& p, hipStream_t st) {
   if (p.A == 4) { AGL(4) }
   else { AGL(8) }
 #undef AGL
+  return true;
 }
 
 void row_alpha(const int* task, int task_begin, const float* log_alpha, int T_glob, int B, int use_task_weights,

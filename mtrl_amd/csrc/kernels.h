@@ -332,14 +332,18 @@ struct PolicyParams {
   int noise_div;        // > 0: device noise of row b is drawn for row b / noise_div (rows i*T + t share the
                         // draw of i: the reference's vmap over tasks hands every task the same key)
 };
-void policy_head(const PolicyParams& p, hipStream_t st);
+// Which heads have kernels: hd in {1, 2, 4, 6, 8} (any W >= 1) and the wide family, even 10 <= hd <= 128
+// (an actor head of 5 .. 64 action dimensions) at W % 4 == 0 (heads_wide.h).  Every launch wrapper below returns false, launching NOTHING, for a head
+// outside this set (no instance stands in for another width); mtsac_create checks its networks once.
+bool head_kernels_cover(int hd, int W);
+bool policy_head(const PolicyParams& p, hipStream_t st);
 // WhT[t][o][w] = Wh[t][w][o] for T_l tasks (E = 1): the policy heads' copy, after every write of Wh
 void head_transpose(const float* Wh, int T_l, int W, int hd, float* WhT, hipStream_t st);
 // the s and s' heads of the merged actor forward in one launch (grouped form; else two launches)
 struct PolicyPair {
   PolicyParams p[2];
 };
-void policy_head_pair(const PolicyParams& a, const PolicyParams& b, hipStream_t st);
+bool policy_head_pair(const PolicyParams& a, const PolicyParams& b, hipStream_t st);
 
 enum CriticHeadMode { CH_TARGET = 0, CH_CRITIC = 1, CH_ACTOR = 2 };
 struct CriticHeadParams {
@@ -390,7 +394,7 @@ struct PlaneOut {
 // colsum_finish.  W % 4 == 0.
 // slot (nullable; hd = 1, planes only, no dz, no dbp): [E][B] from active_rows -- pairs (e, b) with
 // slot < 0 are skipped (their h is not read) and row b of member e is written at plane row slot[e][b].
-void head_backward_data(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
+bool head_backward_data(const HeadParams& hp, const float* dout, long long s_dout, float* dz, const int* counts,
                         const int* rows, int max_rows, int T_l, hipStream_t st, PlaneOut po = PlaneOut{},
                         float* dbp = nullptr, const int* slot = nullptr);
 // Per member e of dq [E][B]: n[e] = the number of rows with dq[e][b] != 0, rows[e * B + s] = those rows in
@@ -410,7 +414,7 @@ bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dou
 // test -- the engine's next check_err must report HEAD_FAULT_WGRAD (mtsac_debug_head_selfcheck)
 void head_backward_weight_inject(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
                                  const int* rows, int max_rows, int T_l, float* dWh, float* dbh, hipStream_t st);
-void head_backward_weight(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
+bool head_backward_weight(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
                           const int* rows, int max_rows, float* dWh, float* dbh, hipStream_t st);
 
 // critic data grad into the action columns + tanh-normal backward -> actor head grad
@@ -436,7 +440,7 @@ struct ActionGradParams {
   float* row_loss;
   float* row_explore;
 };
-void action_grad(const ActionGradParams& p, hipStream_t st);
+bool action_grad(const ActionGradParams& p, hipStream_t st);
 
 // per-row alpha (and task weights) from log_alpha (mtsac.py:60-63,103-113)
 void row_alpha(const int* task, int task_begin, const float* log_alpha, int T_glob, int B,

@@ -261,8 +261,10 @@ __global__ __launch_bounds__(256) void fill_kernel(float* __restrict__ store, lo
     rec[D + A + 2 + F + c] = v;
   }
   float u[4];
-  uniform4(seed, 3u, (unsigned long long)r, 0u, u);
-  for (int j = 0; j < A && j < 4; ++j) rec[D + j] = 2.0f * u[j] - 1.0f;
+  for (int c = 0; c < A; c += 4) {  // counter c: columns 0 .. 3 are the draw they always were
+    uniform4(seed, 3u, (unsigned long long)r, (uint32_t)c, u);
+    for (int j = 0; j < 4 && c + j < A; ++j) rec[D + c + j] = 2.0f * u[j] - 1.0f;
+  }
   uniform4(seed, 4u, (unsigned long long)r, 0u, u);
   rec[D + A] = 10.0f * u[0];
   rec[D + A + 1] = (u[1] < (1.0f / 500.0f)) ? 1.0f : 0.0f;
