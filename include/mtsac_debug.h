@@ -39,12 +39,20 @@ int mtsac_debug_gemm_bench(int precision, int kind, int epi, int batch, int M, i
  * planes and Csum receives their sum h + m + l. */
 int mtsac_debug_gemm_x3p(int epi, int M, int N, int K, const float* A, int a_kmajor, const float* B, int b_kmajor,
                          float* C, const float* bias, const float* mask, float* Csum);
+/* The hidden layers' weight grad in precision split2h alone: per member z < E, C[z][M][N] = A[z]^T . B[z] from
+ * host fp32 A [E][K][M] and B [E][K][N] (both k-major).  The fp16 planes are built on the device at the
+ * exponents of the operands' maxima, as the engine's producers leave them, and multiplied by the k-major x
+ * k-major plain-store launch; slices > 1: split-K into that many slices (<= ceil(K / 32)) and its finishing
+ * pass.  C starts as NaN between two guard bands; a written band is an error (-5). */
+int mtsac_debug_gemm_x3p_kmajor(int E, int M, int N, int K, int slices, const float* A, const float* B, float* C);
 /* Time iters launches of the plane GEMM on device-resident random planes (NT form). */
 int mtsac_debug_gemm_x3p_bench(int epi, int batch, int M, int N, int K, int iters, double* ms_per_launch);
 /* Select the plane GEMM tile geometry (bits 0-7: 0 = 128x128 k32, 1 = 256x128 k32, 2 = 256x128 k16,
  * 3 = 256x256 k16, 255 = by operand form (default)) and
  * ablation bits for experiments (bits 8-15: plane GEMM, bits 16-23: split GEMM; 0 = normal);
- * returns the old geometry. */
+ * returns the old geometry.  Plane GEMM bits: 1 no refill DMA, 2 no MFMAs, 8 refill issued up front (wrong
+ * results, timing only), 4 no XCD tile order, 16 the k-major weight grads' unpipelined main loop (the same
+ * bits as the pipelined one). */
 int mtsac_debug_x3p_geo(int geo);
 
 /* Row-major x row-major plane GEMM (gemm_x3f.hip, 16x16x32 MFMA, K padded to 64): per batch entry

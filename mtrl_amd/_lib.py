@@ -167,6 +167,7 @@ SIGNATURES = {
                                                  ctypes.c_double, ctypes.c_double, I32, P, P, P, P, P, P, P]),
     "mtsac_debug_gemm_bench": (ctypes.c_int, [ctypes.c_int] * 8 + [PD]),
     "mtsac_debug_gemm_x3p": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
+    "mtsac_debug_gemm_x3p_kmajor": (ctypes.c_int, [ctypes.c_int] * 5 + [P, P, P]),
     "mtsac_debug_gemm_x3p_bench": (ctypes.c_int, [ctypes.c_int] * 6 + [PD]),
     "mtsac_debug_x3p_geo": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_gemm_x3f": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 6),

@@ -268,6 +268,50 @@ int mtsac_debug_gemm_x3p(int epi, int M, int N, int K, const float* A, int a_kma
   return 0;
 }
 
+// the split2h k-major x k-major weight grad alone (mtsac_debug.h)
+int mtsac_debug_gemm_x3p_kmajor(int E, int M, int N, int K, int slices, const float* A, const float* B, float* C) {
+  if (E < 1 || E > 8 || M < 1 || N < 1 || K < 1 || slices < 1 || slices > 64 || slices > (int)(up32(K) / 32) || !A ||
+      !B || !C || (long long)E * K * std::max(M, N) >= (1LL << 28))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const int Kp = (int)up32(K);
+  long long lda, pa, ldb, pb;
+  plane_geom(M, K, true, lda, pa);
+  plane_geom(N, K, true, ldb, pb);
+  // the operands' records as a producer leaves them: max |x| and the plane exponent of that bound
+  PlaneRec hrec[2];
+  std::memset(hrec, 0, sizeof hrec);
+  const float ma = host_amax(A, (size_t)E * K * M), mb = host_amax(B, (size_t)E * K * N);
+  hrec[0].e = host_plane_exp(ma); hrec[0].amax[0] = ma;
+  hrec[1].e = host_plane_exp(mb); hrec[1].amax[0] = mb;
+  Guarded gd;
+  const PlaneRec* rec = gd.in(hrec, 2);
+  const float *dA = gd.in(A, (size_t)E * K * M), *dB = gd.in(B, (size_t)E * K * N);
+  __bf16* Ap = gd.mem.get<__bf16>((size_t)3 * pa * E);
+  __bf16* Bp = gd.mem.get<__bf16>((size_t)3 * pb * E);
+  float* dC = gd.out<float>((size_t)E * M * N, "C");  // starts as NaN between two guard bands
+  float* ws = gd.mem.get<float>((size_t)std::max(gemm_ws_floats(M, N, E, std::max(slices, 2)), 1LL));
+  if (!gd.ok || !Ap || !Bp || !ws) return -12;
+  for (int z = 0; z < E; ++z) {
+    split_into(dA + (size_t)z * K * M, M, K, true, Ap + 3 * pa * z, &rec[0].e);
+    split_into(dB + (size_t)z * K * N, N, K, true, Bp + 3 * pb * z, &rec[1].e);
+  }
+  SplitGemmParams g{};
+  g.np = 2;
+  g.ra = rec; g.na = 1; g.rb = rec + 1; g.nb = 1;
+  g.kmul = (float)K;
+  g.A = Ap; g.lda = lda; g.pA = pa; g.sA = 3 * pa; g.a_kmajor = 1;
+  g.B = Bp; g.ldb = ldb; g.pB = pb; g.sB = 3 * pb; g.b_kmajor = 1;
+  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
+  g.M = M; g.N = N; g.K = Kp;
+  g.splits = slices;
+  g.ws = ws;
+  gemm_x3p(g, EPI_STORE, E, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("gemm_x3p k-major")) || (rc = gd.check())) return rc;
+  return gd.back(C, dC, (size_t)E * M * N) ? 0 : -5;
+}
+
 int mtsac_debug_gemm_x3p_bench(int epi, int batch, int M, int N, int K, int iters, double* ms_per_launch) {
   const int layout = (epi >> 8) & 3;  // bit 0: A k-major, bit 1: B k-major
   const int splits = (epi >> 16) & 255;  // split-K slices (0/1: none; EPI_STORE: + splitk_reduce; 255: auto)

@@ -203,7 +203,12 @@ int g_x3p_geo = [] {
   const char* e = getenv("MTSAC_X3P_GEO");
   return e ? atoi(e) : -1;
 }();
-int g_x3p_dbg = 0;
+// experiment bits OR-ed into every launch's dbg (mtsac_debug_x3p_geo's ablation byte, or MTSAC_X3P_DBG at
+// load): 1 / 2 / 8 ablations, 4 no XCD order, 16 the weight grads' unpipelined main loop (same-library A/B)
+int g_x3p_dbg = [] {
+  const char* e = getenv("MTSAC_X3P_DBG");
+  return e ? atoi(e) & 255 : 0;
+}();
 
 // tile shape of a geometry id (see Geo aliases above)
 static int cu_count() {

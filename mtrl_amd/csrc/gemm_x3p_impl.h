@@ -99,6 +99,22 @@ struct Oper {
     }
   }
 
+  // dma_one's two halves for the pipelined k-major loop, which keeps each wave-instruction's source pointer
+  // in registers and advances it by KS rows per K-step: the lane's source of wave-instruction j of the stage
+  // at k0, and the instruction's byte offset in the operand's stage image
+  __device__ static inline const __bf16* dma_src(const __bf16* __restrict__ base, long long ld, long long ps, int r0,
+                                                 int nrows, int k0, int j) {
+    static_assert(KM, "k-major images only");
+    const int lane = threadIdx.x & 63;
+    const int q = j / PER_PLANE;
+    const int irow = (j % PER_PLANE) * RPI + lane / LPR;
+    int col = r0 + 8 * pchunk(irow, lane % LPR);
+    const int last = ((nrows + 7) & ~7) - 8;
+    col = col < last ? col : last;
+    return base + q * ps + (long long)(k0 + irow) * ld + col;
+  }
+  __device__ static inline unsigned dma_dst(int j) { return (j / PER_PLANE) * PLANE + (j % PER_PLANE) * RPI * ROWB; }
+
   // MFMA fragment of plane q: 8 bf16 = k 16ks + 8h .. +7 of row rb + (lane & 31)
   __device__ static inline bf16x8 frag(const char* lds, int q, int rb, int ks, int lane) {
     const char* pl = lds + q * PLANE;
@@ -133,20 +149,34 @@ struct Geo {
   static constexpr int TI = BM / WM / 32, TJ = BN / WN / 32;
 };
 
+template <int V>
+struct IntC {
+  static constexpr int value = V;
+};
+
 // NP: operand planes read (3: 6 products per tile and slice, fp32-accurate; 1: h*h only, bf16)
 // FIN (split-K weight grads, EPI_STORE, p.cnt): every slice writes its raw slab and draws a ticket
 // from the tile's arrival counter (plain stores, one agent-scope release, relaxed agent fetch_add);
 // the slice drawing S - 1 acquires and adds the tile's S slabs in slice order into C (the bits of
 // splitk_reduce_kernel), then re-arms the counter -- no separate reduce launch.
-template <class G, bool AKM, bool BKM, int EPI, bool PLANES_OUT, int NP = 3, bool FIN = false>
+// PIPE (k-major x k-major weight grads, one 16-deep k-slice per K-step): the main loop kloop_pipe below,
+// which reads the MFMA fragments of K-step kt + 1 from LDS while the MFMAs of step kt issue; the same
+// products in the same order per accumulator as kloop, so the same bits.  ABL (PIPE only; experiments,
+// results are wrong): 1 = no refill DMA in the steady state, 2 = no MFMAs, 8 = a step's refill issued
+// up front instead of spread over its MFMA groups.
+template <class G, bool AKM, bool BKM, int EPI, bool PLANES_OUT, int NP = 3, bool FIN = false, bool PIPE = false,
+          int ABL = 0>
 __global__ __launch_bounds__(G::NTH, 1) void gemm_x3p_kernel(SplitGemmParams p) {
   using OA = Oper<G::BM, AKM, G::KS, NP>;
   using OB = Oper<G::BN, BKM, G::KS, NP>;
   constexpr int STAGE = OA::BYTES + OB::BYTES;
   // the stage's wave-instructions are dealt round robin: waves < DMA_X issue one more
   constexpr int DMA_LO = (OA::NJ + OB::NJ) / G::NW, DMA_X = (OA::NJ + OB::NJ) % G::NW;
-  static_assert(G::STAGES * STAGE + (FIN ? 16 : 0) <= 160 * 1024, "LDS");
-  __shared__ __attribute__((aligned(16))) char smem[G::STAGES * STAGE + (FIN ? 16 : 0)];  // FIN: + the 'last' word
+  // ring depth: the geometry's; the pipelined loop takes what LDS allows (split2h: 6 x 24 KiB stages,
+  // split3: 4 x 36 KiB) under the geometry's kernel symbol
+  constexpr int RING = PIPE ? (NP == 2 ? 6 : 4) : G::STAGES;
+  static_assert(RING * STAGE + (FIN ? 16 : 0) <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(16))) char smem[RING * STAGE + (FIN ? 16 : 0)];  // FIN: + the 'last' word
   char* lds = smem;
   const unsigned lds_base = (unsigned)(unsigned long long)(lds_void*)smem;  // LDS byte address
 
@@ -334,12 +364,165 @@ __global__ __launch_bounds__(G::NTH, 1) void gemm_x3p_kernel(SplitGemmParams p) 
   const long long k0 = (long long)sp * p.kchunk;
   const int nks = (S > 1 ? min(p.kchunk, p.K - (int)k0) : p.K) / G::KS;
   const int m0 = bx * G::BM, n0 = by * G::BN;
-  kloop(p.A + z * p.sA + (AKM ? k0 * p.lda : k0), p.B + z * p.sB + (BKM ? k0 * p.ldb : k0), m0, n0, nks);
+  if constexpr (PIPE) {
+    // The pipelined k-major main loop.  Ring protocol, one step later than kloop's: at the top of step kt
+    // a wave waits for its own DMA of stage kt + 1 (counted vmcnt: the younger stages stay in flight) and
+    // for its own LDS reads of stage kt, which it issued during step kt - 1 (lgkmcnt(0)); after the one
+    // barrier every wave's part of stage kt + 1 has landed and nobody reads stage kt's slot any more, so
+    // the step reads stage kt + 1's fragments into the other register set behind its first MFMA group
+    // and refills that slot with stage kt + STAGES, spread over the later groups.  A stage is issued
+    // STAGES - 1 steps before the wait that retires it (kloop: the same count at the same depth).  Only
+    // the prologue's fragment reads are exposed.
+    static_assert(AKM && BKM && G::KS == 16 && (NP == 2 || NP == 3), "the k-major weight-grad form");
+    static_assert(OA::NJ % G::NW == 0, "every wave's first pieces are A's, the rest B's");
+    static_assert(RING >= 3, "ring depth");
+    constexpr int D = RING;
+    constexpr int QA = OA::NJ / G::NW;  // the wave's pieces q < QA are A's
+    struct Frag {
+      bf16x8 a[G::TI][NP], b[G::TJ][NP];
+    };
+    const __bf16* __restrict__ A = p.A + z * p.sA + k0 * p.lda;
+    const __bf16* __restrict__ B = p.B + z * p.sB + k0 * p.ldb;
+    const int nk = nks;
+    const bool extra = DMA_X != 0 && wave < DMA_X;  // the wave issues the last (partial) round of pieces too
+    // the wave's q-th piece: its lane's source pointer at the next stage to refill (advanced by KS rows
+    // per refill) and its LDS byte offset in a stage
+    const __bf16* src[PIECES];
+    unsigned dst[PIECES];
+#pragma unroll
+    for (int q = 0; q < PIECES; ++q) {
+      const int jg = wave + q * G::NW;
+      if (q < QA) {
+        src[q] = OA::dma_src(A, p.lda, p.pA, m0, p.M, D * G::KS, jg);
+        dst[q] = OA::dma_dst(jg);
+      } else {
+        const int jb = jg - OA::NJ < OB::NJ ? jg - OA::NJ : 0;  // (a wave without the last piece never issues it)
+        src[q] = OB::dma_src(B, p.ldb, p.pB, n0, p.N, D * G::KS, jb);
+        dst[q] = OA::BYTES + OB::dma_dst(jb);
+      }
+    }
+    const long long inc_a = (long long)G::KS * p.lda, inc_b = (long long)G::KS * p.ldb;
+    // piece q of the refill into the slot at LDS address st
+    auto piece = [&](unsigned st, int q) __attribute__((always_inline)) {
+      if (q < DMA_LO || extra) glds16(src[q], st + dst[q]);
+      src[q] += q < QA ? inc_a : inc_b;
+    };
+    // wait until at most y of this wave's stages are in flight
+    auto wait_c = [&](auto Y) __attribute__((always_inline)) {
+      constexpr int y = decltype(Y)::value;
+      if (DMA_X != 0 && extra) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(y * (DMA_LO + 1)) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(y * DMA_LO) : "memory");
+    };
+    auto wait_rt = [&](int y) __attribute__((always_inline)) {  // y <= D - 1
+      if constexpr (D - 1 >= 5) if (y >= 5) return wait_c(IntC<5>{});
+      if constexpr (D - 1 >= 4) if (y == 4) return wait_c(IntC<4>{});
+      if constexpr (D - 1 >= 3) if (y == 3) return wait_c(IntC<3>{});
+      if (y == 2) return wait_c(IntC<2>{});
+      if (y == 1) return wait_c(IntC<1>{});
+      return wait_c(IntC<0>{});
+    };
+    static_assert(D - 1 <= 5 && (D - 1) * (DMA_LO + 1) < 64, "vmcnt range");
+    // a stage's fragments: A's tiles, then B's
+    auto load = [&](Frag& f, const char* st) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < G::TI; ++i)
+#pragma unroll
+        for (int q = 0; q < NP; ++q) f.a[i][q] = OA::frag(st, q, wm + 32 * i, 0, lane);
+#pragma unroll
+      for (int j = 0; j < G::TJ; ++j)
+#pragma unroll
+        for (int q = 0; q < NP; ++q) f.b[j][q] = OB::frag(st + OA::BYTES, q, wn + 32 * j, 0, lane);
+    };
+
+#pragma unroll
+    for (int i = 0; i < G::TI; ++i)
+#pragma unroll
+      for (int j = 0; j < G::TJ; ++j) acc[i][j] = f32x16{0};
+
+    // prologue: fill the ring, then stage 0's fragments
+#pragma unroll
+    for (int s = 0; s < D; ++s)
+      if (s < nk) {
+        const unsigned st = lds_base + s * STAGE;
+        OA::dma(A, p.lda, p.pA, m0, p.M, s * G::KS, st, wave, G::NW);
+        OB::dma(B, p.ldb, p.pB, n0, p.N, s * G::KS, st + OA::BYTES, fb, G::NW);
+      }
+    wait_rt(min(D, nk) - 1);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    Frag f0, f1;
+    load(f0, lds);
+
+    int slot = 0, nslot = 1 % D;  // ring slots of stages kt and kt + 1
+    // MAIN: stages up to kt + D exist (a full ring in flight, a refill and a next stage to read); the
+    // last steps (the ring drains) take these from nk at run time
+    auto step = [&](int kt, Frag& cur, Frag& nxt, auto MAINC) __attribute__((always_inline)) {
+      constexpr bool MAIN = decltype(MAINC)::value != 0;
+      if constexpr (MAIN) wait_c(IntC<D - 2>{});
+      else wait_rt(min(D - 2, max(0, nk - 2 - kt)));
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      const bool refill = !(ABL & 1) && (MAIN || kt + D < nk);
+      const bool pre = MAIN || kt + 1 < nk;
+      const unsigned rst = lds_base + slot * STAGE;
+      const char* nst = lds + nslot * STAGE;
+      if ((ABL & 8) && refill) {
+#pragma unroll
+        for (int q = 0; q < PIECES; ++q) piece(rst, q);
+      }
+#pragma unroll
+      for (int i = 0; i < G::TI; ++i)
+#pragma unroll
+        for (int j = 0; j < G::TJ; ++j) {
+          const int g = i * G::TJ + j;
+          if (!(ABL & 8) && refill) {
+#pragma unroll
+            for (int q = g * PIECES / SLOTS; q < (g + 1) * PIECES / SLOTS; ++q) piece(rst, q);
+          }
+          if constexpr ((ABL & 2) != 0) {
+            acc[i][j][0] += (float)cur.a[i][0][0] + (float)cur.b[j][NP - 1][7];
+          } else {
+            f32x16 c = acc[i][j];
+            if constexpr (NP == 2) {  // fp16 planes: h*l, l*h, h*h
+              typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+              c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, cur.a[i][0]), __builtin_bit_cast(h8, cur.b[j][1]), c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, cur.a[i][1]), __builtin_bit_cast(h8, cur.b[j][0]), c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, cur.a[i][0]), __builtin_bit_cast(h8, cur.b[j][0]), c, 0, 0, 0);
+            } else {
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur.a[i][1], cur.b[j][1], c, 0, 0, 0);  // m*m
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur.a[i][0], cur.b[j][2], c, 0, 0, 0);  // h*l
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur.a[i][2], cur.b[j][0], c, 0, 0, 0);  // l*h
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur.a[i][0], cur.b[j][1], c, 0, 0, 0);  // h*m
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur.a[i][1], cur.b[j][0], c, 0, 0, 0);  // m*h
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cur.a[i][0], cur.b[j][0], c, 0, 0, 0);  // h*h
+            }
+            acc[i][j] = c;
+          }
+          // the next step's fragments, all behind the first group: they land long before the step ends
+          if (g == 0 && pre) load(nxt, nst);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      slot = nslot;
+      nslot = nslot + 1 == D ? 0 : nslot + 1;
+    };
+    int kt = 0;
+    for (; kt + D + 1 < nk; kt += 2) {
+      step(kt, f0, f1, IntC<1>{});
+      step(kt + 1, f1, f0, IntC<1>{});
+    }
+    for (; kt < nk; kt += 2) {
+      step(kt, f0, f1, IntC<0>{});
+      if (kt + 1 < nk) step(kt + 1, f1, f0, IntC<0>{});
+    }
+  } else {
+    kloop(p.A + z * p.sA + (AKM ? k0 * p.lda : k0), p.B + z * p.sB + (BKM ? k0 * p.ldb : k0), m0, n0, nks);
+  }
   epilogue(z, zz, S > 1, m0, n0);
   if constexpr (FIN) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its slab stores
     __syncthreads();
-    int* last = reinterpret_cast<int*>(smem + G::STAGES * STAGE);
+    int* last = reinterpret_cast<int*>(smem + RING * STAGE);
     const int tile = lin;  // (z, bx, by)
     if (t == 0) {
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
@@ -411,6 +594,19 @@ void launch_x3p_np(const SplitGemmParams& p, int epi, dim3 grid, hipStream_t st)
   if constexpr (AKM && BKM && NP == 3 && G::STAGES * (G::BM + G::BN) * G::KS * 2 * 3 + 16 <= 160 * 1024) {
     if (epi == EPI_STORE && !planes && p.cnt != nullptr && p.splits > 1) {  // weight grads: in-launch finish
       hipLaunchKernelGGL((gemm_x3p_kernel<G, true, true, EPI_STORE, false, 3, true>), grid, block, 0, st, p);
+      return;
+    }
+  }
+  // weight grads on 256 x 128 k16 tiles (GeoWide16): the pipelined loop; p.dbg & 16 keeps kloop (experiments, the bitwise tests),
+  // p.dbg & 1 / 2 / 8 pick an ablated split2h instance (tools/x3p_ablate.py)
+  if constexpr (AKM && BKM && (NP == 2 || NP == 3) && G::BM == 256 && G::BN == 128 && G::WM == 4 && G::WN == 2 &&
+                G::KS == 16) {
+    if (epi == EPI_STORE && !planes && !(p.dbg & 16)) {
+      const int abl = NP != 2 ? 0 : (p.dbg & 1) ? 1 : (p.dbg & 2) ? 2 : (p.dbg & 8);  // split2h only, one bit
+      if (abl == 1) hipLaunchKernelGGL((gemm_x3p_kernel<G, true, true, EPI_STORE, false, NP, false, true, NP == 2 ? 1 : 0>), grid, block, 0, st, p);
+      else if (abl == 2) hipLaunchKernelGGL((gemm_x3p_kernel<G, true, true, EPI_STORE, false, NP, false, true, NP == 2 ? 2 : 0>), grid, block, 0, st, p);
+      else if (abl == 8) hipLaunchKernelGGL((gemm_x3p_kernel<G, true, true, EPI_STORE, false, NP, false, true, NP == 2 ? 8 : 0>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((gemm_x3p_kernel<G, true, true, EPI_STORE, false, NP, false, true, 0>), grid, block, 0, st, p);
       return;
     }
   }
