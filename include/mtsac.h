@@ -383,6 +383,31 @@ int mtsac_task_gradnorm_solve(mtsac_engine* h, int which, const float* task_loss
                               int32_t weighted_norms, float* task_weights, float* original_losses, float* mu,
                               float* nu, int64_t* count, float* w, float* logs /* 3 */);
 
+/* ---- network health metrics (MTSAC.get_metrics, mtsac.py; get_dormant_neuron_logs and compute_srank,
+ * mtrl/monitoring/metrics.py).  DESIGN.md section 15.  Evaluation time: nothing is updated.
+ * mtsac_network_metrics: the actor forward on batch->observations (only that field is read; the others may be
+ * NULL), a = tanh(mu + sigma eps) with eps [B][A] injected or NULL (the device noise stream at the position
+ * mtsac_task_gradients reads), the ONLINE critic's forward on (a, observations); then, for every trunk layer i
+ * of every member e (the actor has one, the critic num_critics) and its post-ReLU output H [B][W] (the B = n T
+ * real rows only):
+ *   what bit 0  s_j = mean_b |H[b][j]|, the normalised scores s_j / (mean_j s_j + 1e-9) and the number of
+ *               neurons whose normalised score is <= threshold (the reference's 0.1);
+ *   what bit 1  the fp64 Gram matrix H^T H (W <= B) or H H^T (W > B), r x r with r = min(B, W): the squares of
+ *               H's singular values are its eigenvalues (the host computes srank from them).
+ * batch NULL samples on the device (advancing the index stream, as mtsac_task_gradients does); rows must be
+ * interleaved i*T + t.  -95 on a task-sharded engine, -22 for what == 0, bits above 1 or a non-finite
+ * threshold.  Works at every precision, action_dim and gradient-surgery mode; a captured step graph, the
+ * parameters, the optimizer state and the logs stay as they are.  The trunk runs on fp32 operands as in the
+ * rollout and mtsac_task_gradients passes (fp32 MFMA, or the on-the-fly 3-way bf16 split), so the GEMM error
+ * bound is the one documented at enum mtsac_precision whatever the engine's precision.
+ * which: 0 actor, 1 critic.  mtsac_get_network_scores: scores [E][D][W] (normalised), counts [E][D] of the
+ * last call with bit 0; mtsac_network_gram_dim: r; mtsac_get_network_gram: one [r][r] matrix of the last call
+ * with bit 1.  The scratch is allocated at the first call that needs it and freed with the engine. */
+int mtsac_network_metrics(mtsac_engine* h, const mtsac_batch* batch, const float* eps, int32_t what, float threshold);
+int mtsac_get_network_scores(mtsac_engine* h, int which, float* scores, int32_t* counts);
+int mtsac_network_gram_dim(const mtsac_engine* h, int which);
+int mtsac_get_network_gram(mtsac_engine* h, int which, int32_t member, int32_t layer, double* gram);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,20 @@ int mtsac_debug_set_collective_model(struct mtsac_engine* engine, int32_t nranks
 struct mtsac_engine;
 int mtsac_debug_timed_launch(struct mtsac_engine* engine, int32_t i, int32_t* dims, double* ms);
 
+/* The two network-metrics kernels alone (netmetrics.hip) on host arrays: Z matrices of M rows x W columns, H
+ * [Z][M][ld] (ld >= W; the padding columns are never read, and the device copy is followed by M more rows of
+ * NaN).  Outputs start as NaN / -1 between guard bands; -5 on a written band (named in mtsac_last_error).
+ * mtsac_debug_act_stats: score [Z][W] = mean_b |H|, norm [Z][W] = score / (mean_j score + 1e-9), count [Z] =
+ * #(norm <= threshold).
+ * mtsac_debug_act_gram: gram [Z][r][r] fp64, r = min(M, W); info[0] = the side formed (0: H^T H, 1: H H^T),
+ * info[1] = r. */
+int mtsac_debug_act_stats(int Z, int M, int W, int ld, const float* H, float threshold, float* score, float* norm,
+                          int32_t* count);
+int mtsac_debug_act_gram(int Z, int M, int W, int ld, const float* H, double* gram, int32_t* info);
+/* HIP-event durations of the last mtsac_network_metrics call's kernels: ms[0] the column statistics of every
+ * layer, ms[1] the Grams (0 for a part the call did not run). */
+int mtsac_debug_network_metrics_ms(struct mtsac_engine* engine, double* ms /* 2 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,13 @@ SIGNATURES = {
     "mtsac_get_gradnorm_task_losses": (ctypes.c_int, [P, P]),
     "mtsac_task_gradnorm_solve": (ctypes.c_int, [P, ctypes.c_int, P, ctypes.c_double, I32, ctypes.c_double,
                                                  ctypes.c_double, ctypes.c_double, I32, P, P, P, P, P, P, P]),
+    "mtsac_network_metrics": (ctypes.c_int, [P, ctypes.POINTER(Batch), P, I32, ctypes.c_float]),
+    "mtsac_get_network_scores": (ctypes.c_int, [P, ctypes.c_int, P, P]),
+    "mtsac_network_gram_dim": (ctypes.c_int, [P, ctypes.c_int]),
+    "mtsac_get_network_gram": (ctypes.c_int, [P, ctypes.c_int, I32, I32, P]),
+    "mtsac_debug_act_stats": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_float, P, P, P]),
+    "mtsac_debug_act_gram": (ctypes.c_int, [ctypes.c_int] * 4 + [P, P, P]),
+    "mtsac_debug_network_metrics_ms": (ctypes.c_int, [P, P]),
     "mtsac_debug_gemm_bench": (ctypes.c_int, [ctypes.c_int] * 8 + [PD]),
     "mtsac_debug_gemm_x3p": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
     "mtsac_debug_gemm_x3p_kmajor": (ctypes.c_int, [ctypes.c_int] * 5 + [P, P, P]),

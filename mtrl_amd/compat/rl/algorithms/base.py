@@ -13,6 +13,7 @@ base.py:279-288): ``config.batch_size`` rows, the reference's 128 per task in ev
 from __future__ import annotations
 
 import abc
+import os
 import time
 from collections import deque
 
@@ -132,6 +133,12 @@ class OffPolicyAlgorithm(Algorithm):
                         self, update_logs = self.compute_weights(metrics_data)
                         if track:
                             wandb.log(update_logs, step=total_steps)
+                        # the reference has this call commented out while compute_network_metrics
+                        # defaults to ALL: opt-in, so existing runs do not change
+                        if hasattr(self, "get_metrics") and os.environ.get("MTSAC_NETWORK_METRICS") == "1":
+                            self, network_logs = self.get_metrics(config.compute_network_metrics, metrics_data)
+                            if track:
+                                wandb.log(network_logs, step=total_steps)
                     if checkpoint_manager is not None:
                         checkpoint_manager.save(total_steps, agent=self, buffer=replay_buffer,
                                                 metadata={"timestamp": run_timestamp, "step": global_step,

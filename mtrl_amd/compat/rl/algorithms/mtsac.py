@@ -340,6 +340,24 @@ class MTSAC(OffPolicyAlgorithm):
         e_cur = np.repeat(self._rng.standard_normal((n, A)), T, axis=0).astype(np.float32)
         return self, compute_weights(self.engine, tuple(data), e_next, e_cur)
 
+    def get_metrics(self, metrics, data):
+        """mtsac.py ``get_metrics``: dormant-neuron and srank logs of every trunk layer of the actor and of
+        each online critic member at evaluation time (no update), on ``data.observations`` and one action
+        sample a ~ pi(.|s).  The statistics and the activation Grams come from one device pass
+        (mtrl_amd/netmetrics.py); ``metrics.is_enabled`` decides the groups as the reference's enum does
+        (a flag test: NONE nothing, DORMANT_NEURONS / SRANK their own group, ALL both)."""
+        from ....netmetrics import compute_metrics
+        from ...config.utils import Metrics
+
+        if not (metrics.is_enabled(Metrics.DORMANT_NEURONS) or metrics.is_enabled(Metrics.SRANK)):
+            return self, {}
+        obs = np.asarray(data.observations, np.float32)
+        n = obs.shape[0] // self.num_tasks
+        if n != self._cfg_kwargs["batch_per_task"]:  # raises once a buffer lives in the engine
+            self._rebuild(batch_per_task=n, capacity=max(self._cfg_kwargs["capacity"], n))
+        eps = self._rng.standard_normal((obs.shape[0], self.engine.action_dim)).astype(np.float32)
+        return self, compute_metrics(self.engine, metrics, obs, eps)
+
     # ------------------------------------------------------------------ state (checkpoint)
     def state_dict(self) -> dict[str, np.ndarray]:
         """Agent pytree keyed by flax path (compat/checkpoint.py), e.g.

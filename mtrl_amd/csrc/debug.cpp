@@ -1087,6 +1087,74 @@ int mtsac_debug_head_active_rows(int E, int B, const float* dq, int* n, int* row
   return g.back(n, d_n, (size_t)E) && g.back(rows, d_rows, (size_t)E * B) && g.back(slot, d_slot, (size_t)E * B) ? 0 : -5;
 }
 
+// ---- the network-metrics kernels (netmetrics.hip) ----
+// H [Z][M][ld] on the device, followed by M rows of NaN (a read past the last matrix shows in the results)
+static float* metrics_input(Guarded& g, const float* H, int Z, int M, int ld) {
+  const size_t n = (size_t)Z * M * ld, tail = (size_t)M * ld;
+  float* d = g.mem.get<float>(n + tail);
+  if (!d || hipMemcpy(d, H, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(d + n, 0xFF, tail * sizeof(float)) != hipSuccess)
+    g.ok = false;
+  return d;
+}
+
+int mtsac_debug_act_stats(int Z, int M, int W, int ld, const float* H, float threshold, float* score, float* norm,
+                          int32_t* count) {
+  if (Z < 1 || Z > 64 || M < 1 || W < 1 || ld < W || !H || !score || !norm || !count || !std::isfinite(threshold))
+    return -22;
+  if (!outputs_distinct({score, norm, count})) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  ActStats s{};
+  s.H = metrics_input(g, H, Z, M, ld);
+  s.Z = Z;
+  s.M = M;
+  s.W = W;
+  s.ld = ld;
+  s.sH = (long long)M * ld;
+  s.threshold = threshold;
+  s.part = g.out<double>((size_t)Z * act_stats_chunks(M) * W, "part");
+  s.score = g.out<float>((size_t)Z * W, "score");
+  s.s_score = W;
+  s.norm = g.out<float>((size_t)Z * W, "norm");
+  s.s_norm = W;
+  s.count = g.out<int>((size_t)Z, "count");
+  s.s_count = 1;
+  if (!g.ok) return -12;
+  act_stats(s, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("act_stats")) || (rc = g.check())) return rc;
+  return g.back(score, s.score, (size_t)Z * W) && g.back(norm, s.norm, (size_t)Z * W) &&
+                 g.back(count, s.count, (size_t)Z)
+             ? 0
+             : -5;
+}
+
+int mtsac_debug_act_gram(int Z, int M, int W, int ld, const float* H, double* gram, int32_t* info) {
+  if (Z < 1 || Z > 64 || M < 1 || W < 1 || ld < W || !H || !gram) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t r = (size_t)act_gram_dim(M, W);
+  Guarded g;
+  ActGram a{};
+  a.H = metrics_input(g, H, Z, M, ld);
+  a.Z = Z;
+  a.M = M;
+  a.W = W;
+  a.ld = ld;
+  a.sH = (long long)M * ld;
+  a.gram = g.out<double>((size_t)Z * r * r, "gram");
+  a.sG = (long long)(r * r);
+  if (!g.ok) return -12;
+  act_gram(a, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("act_gram")) || (rc = g.check())) return rc;
+  if (info) {
+    info[0] = W <= M ? 0 : 1;
+    info[1] = (int32_t)r;
+  }
+  return g.back(gram, a.gram, (size_t)Z * r * r) ? 0 : -5;
+}
+
 int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W, int hd, const int* task, const float* h,
                               const float* Wh, const float* dout, const float* dq, float* dz, float* dbp, float* db,
                               float* planes, float* dWh, float* dbh, int* counts, int* rows, int* info) {

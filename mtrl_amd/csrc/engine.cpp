@@ -473,6 +473,8 @@ struct mtsac_engine {
     for (hipEvent_t x : {ev_ap[0], ev_ap[1], ev_tail[0], ev_tail[1]})
       if (x) (void)hipEventDestroy(x);
     for (hipEvent_t e : evpool) (void)hipEventDestroy(e);
+    for (hipEvent_t x : nm.ev)
+      if (x) (void)hipEventDestroy(x);
     for (hipStream_t x : {st, s1, s2, s3, s4, sa})
       if (x) (void)hipStreamDestroy(x);
     if (counted_lanes) {
@@ -2008,6 +2010,107 @@ struct mtsac_engine {
       task_wgrad(actor, 1, xa, ld_a, ha, dza, i);
       if (i > 0) dgrad_layer(actor, actor.p, ha, nullptr, dza, nullptr, i, Bl);
     }
+  }
+
+  // ------------------------------------------------------------ network health metrics (netmetrics.hip)
+  // Evaluation time (mtsac_network_metrics; reference MTSAC.get_metrics, mtsac.py).  The forward is the
+  // per-task gradient passes' (tg_actor): fp32 operands, so every layer's post-ReLU output lands dense in
+  // ha[i] [1][B][Wa] / hc[i] [E][B][Wc] over exactly the B real rows -- the padded rows of the plane
+  // buffers (relu(bias), not zero) never exist in this form.  Only step buffers that every step rewrites
+  // from its own batch are written; parameters, moments, logs, the noise counter and a captured graph are
+  // not touched.  Outputs (which 0 actor, 1 critic): norm [E][D][W], count [E][D], gram [E][D][r][r].
+  struct NetMetrics {
+    double* part[2] = {};
+    float *score[2] = {}, *norm[2] = {};
+    int* count[2] = {};
+    double* gram[2] = {};
+    int last = 0;  // `what` of the last call that completed
+    hipEvent_t ev[3] = {};
+    double ms[2] = {0.0, 0.0};
+  } nm;
+  Net& nm_net(int which) { return which == 0 ? actor : critic; }
+  int nm_dim(int which) const { return act_gram_dim(B, which == 0 ? actor.width : critic.width); }
+
+  int ensure_metrics_buffers(int what) {
+    int rc = 0;
+    bool fresh = false;
+    for (int w = 0; w < 2; ++w) {
+      const Net& net = nm_net(w);
+      const size_t ED = (size_t)net.E * net.depth, r = (size_t)nm_dim(w);
+      if (!nm.part[w]) {
+        if ((rc = alloc(&nm.part[w], (size_t)net.E * act_stats_chunks(B) * net.width)) ||
+            (rc = alloc(&nm.score[w], ED * net.width)) || (rc = alloc(&nm.norm[w], ED * net.width)) ||
+            (rc = alloc(&nm.count[w], ED)))
+          return rc;
+        fresh = true;
+      }
+      if ((what & 2) && !nm.gram[w]) {
+        if ((rc = alloc(&nm.gram[w], ED * r * r))) return rc;
+        fresh = true;
+      }
+    }
+    for (hipEvent_t& e : nm.ev)
+      if (!e && hipEventCreate(&e) != hipSuccess) return fail(-5, "hipEventCreate");
+    // alloc()'s null-stream zero fills before the engine streams use the buffers
+    if (fresh && hipDeviceSynchronize() != hipSuccess) return fail(-5, "device synchronize");
+    return 0;
+  }
+
+  void network_metrics_pass(bool device_batch, bool device_noise, int what, float threshold) {
+    tg_prepare(device_batch);
+    const int Bl = B;
+    PolicyParams pp;
+    CriticHeadParams ch;
+    head_base(pp, ch, B / T_l, 0, 0);  // fp32 operands: no action planes
+    trunk_forward(actor, actor.p, 0, xa, ld_a, ha, nullptr, Bl);
+    {
+      PolicyParams q = pi_s(pp, ha[actor.depth - 1], device_noise);
+      q.stream_id = 4;  // the position tg_actor draws a ~ pi(.|s) from
+      policy_head(q, cur);
+    }
+    trunk_forward(critic, critic.p, 0, xcp, ld_c, hc, nullptr, Bl);
+    (void)hipEventRecord(nm.ev[0], cur);
+    for (int w = 0; w < 2 && (what & 1); ++w) {
+      const Net& net = nm_net(w);
+      float** acts = w == 0 ? ha : hc;
+      for (int i = 0; i < net.depth; ++i) {
+        ActStats s{};
+        s.H = acts[i];
+        s.Z = net.E;
+        s.M = Bl;
+        s.W = net.width;
+        s.ld = net.width;
+        s.sH = (long long)Bl * net.width;
+        s.threshold = threshold;
+        s.part = nm.part[w];
+        s.score = nm.score[w] + (long long)i * net.width;
+        s.s_score = (long long)net.depth * net.width;
+        s.norm = nm.norm[w] + (long long)i * net.width;
+        s.s_norm = s.s_score;
+        s.count = nm.count[w] + i;
+        s.s_count = net.depth;
+        act_stats(s, cur);
+      }
+    }
+    (void)hipEventRecord(nm.ev[1], cur);
+    for (int w = 0; w < 2 && (what & 2); ++w) {
+      const Net& net = nm_net(w);
+      float** acts = w == 0 ? ha : hc;
+      const long long rr = (long long)nm_dim(w) * nm_dim(w);
+      for (int i = 0; i < net.depth; ++i) {
+        ActGram g{};
+        g.H = acts[i];
+        g.Z = net.E;
+        g.M = Bl;
+        g.W = net.width;
+        g.ld = net.width;
+        g.sH = (long long)Bl * net.width;
+        g.gram = nm.gram[w] + i * rr;
+        g.sG = net.depth * rr;
+        act_gram(g, cur);
+      }
+    }
+    (void)hipEventRecord(nm.ev[2], cur);
   }
 
   // the step's scalar tail (step_finish): loss sums, temperature update, parameter norms, logs
@@ -3594,6 +3697,80 @@ int mtsac_task_gradnorm_solve(mtsac_engine* h, int which, const float* task_loss
   logs[0] = lg[0];
   logs[1] = lg[1];
   logs[2] = lg[5];
+  return 0;
+}
+
+// ---------------------------------------------------------------- network health metrics
+int mtsac_network_metrics(mtsac_engine* h, const mtsac_batch* b, const float* eps, int32_t what, float threshold) {
+  if (!h) return fail(-22, "null engine");
+  if (int rc = h->geo_guard()) return rc;
+  if (h->T_l != h->T_g) return fail(-95, "network metrics need every task on one engine (unsharded)");
+  if (what <= 0 || (what & ~3)) return fail(-22, "what: bit 0 dormant-neuron statistics, bit 1 Gram matrices");
+  if (!std::isfinite(threshold)) return fail(-22, "threshold must be finite");
+  if (b && !b->observations) return fail(-22, "batch without observations");
+  if (int rc = h->ensure_metrics_buffers(what)) return rc;
+  const int B = h->B, D = h->D, A = h->A;
+  if (b) {  // only the observations are read: they double as next_obs, the rest is zero
+    HIP_TRY(hipMemcpyAsync(h->u_obs, b->observations, sizeof(float) * B * D, hipMemcpyDefault, h->st));
+    HIP_TRY(hipMemcpyAsync(h->u_nobs, h->u_obs, sizeof(float) * B * D, hipMemcpyDeviceToDevice, h->st));
+    HIP_TRY(hipMemsetAsync(h->u_act, 0, sizeof(float) * B * A, h->st));
+    HIP_TRY(hipMemsetAsync(h->u_done, 0, sizeof(float) * B, h->st));
+    HIP_TRY(hipMemsetAsync(h->u_rew, 0, sizeof(float) * B, h->st));
+  }
+  if (eps) HIP_TRY(hipMemcpyAsync(h->eps_c, eps, sizeof(float) * B * A, hipMemcpyDefault, h->st));
+  const bool timing = h->timing;
+  h->timing = false;
+  h->nm.last = 0;
+  h->network_metrics_pass(b == nullptr, eps == nullptr, what, threshold);
+  h->timing = timing;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->st));
+  int e = 0;
+  HIP_TRY(hipMemcpy(&e, h->err, sizeof(int), hipMemcpyDeviceToHost));
+  if (e) {
+    int z = 0;
+    HIP_TRY(hipMemcpy(h->err, &z, sizeof(int), hipMemcpyHostToDevice));
+    return fail(-22, "batch rows must be interleaved i*T + t with exact one-hot task ids (as the buffer samples)");
+  }
+  if (!h->comm_error.empty()) return h->check_err();
+  for (int k = 0; k < 2; ++k) {
+    float ms = 0.f;
+    h->nm.ms[k] = hipEventElapsedTime(&ms, h->nm.ev[k], h->nm.ev[k + 1]) == hipSuccess ? (double)ms : 0.0;
+  }
+  h->nm.last = what;
+  return 0;
+}
+
+int mtsac_get_network_scores(mtsac_engine* h, int which, float* scores, int32_t* counts) {
+  if (!h || (which != 0 && which != 1)) return fail(-22, "which: 0 actor, 1 critic");
+  if (!(h->nm.last & 1)) return fail(-22, "no dormant-neuron statistics yet (mtsac_network_metrics with what bit 0)");
+  const Net& net = h->nm_net(which);
+  const size_t ED = (size_t)net.E * net.depth;
+  if (scores) HIP_TRY(hipMemcpy(scores, h->nm.norm[which], sizeof(float) * ED * net.width, hipMemcpyDefault));
+  if (counts) HIP_TRY(hipMemcpy(counts, h->nm.count[which], sizeof(int32_t) * ED, hipMemcpyDefault));
+  return 0;
+}
+
+int mtsac_network_gram_dim(const mtsac_engine* h, int which) {
+  if (!h || (which != 0 && which != 1)) return -22;
+  return h->nm_dim(which);
+}
+
+int mtsac_get_network_gram(mtsac_engine* h, int which, int32_t member, int32_t layer, double* gram) {
+  if (!h || !gram || (which != 0 && which != 1)) return fail(-22, "which: 0 actor, 1 critic; gram required");
+  if (!(h->nm.last & 2)) return fail(-22, "no Gram matrices yet (mtsac_network_metrics with what bit 1)");
+  const Net& net = h->nm_net(which);
+  if (member < 0 || member >= net.E || layer < 0 || layer >= net.depth) return fail(-22, "member or layer out of range");
+  const size_t rr = (size_t)h->nm_dim(which) * h->nm_dim(which);
+  HIP_TRY(hipMemcpy(gram, h->nm.gram[which] + ((size_t)member * net.depth + layer) * rr, sizeof(double) * rr,
+                    hipMemcpyDefault));
+  return 0;
+}
+
+int mtsac_debug_network_metrics_ms(mtsac_engine* h, double* ms) {
+  if (!h || !ms) return fail(-22, "null argument");
+  ms[0] = (h->nm.last & 1) ? h->nm.ms[0] : 0.0;
+  ms[1] = (h->nm.last & 2) ? h->nm.ms[1] : 0.0;
   return 0;
 }
 

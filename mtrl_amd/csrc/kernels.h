@@ -716,6 +716,40 @@ struct GradnormSolve {
 void task_losses(const float* row, int T, int n, double inv, float* out, hipStream_t st);
 void gradnorm_solve(const GradnormSolve& s, hipStream_t st);
 
+// ------------------------------------------------------------------ network health metrics (netmetrics.hip;
+// MTSAC.get_metrics, get_dormant_neuron_logs, compute_srank).  Z fp32 matrices H[z] = H + z * sH of M rows x
+// W columns, row stride ld: one trunk layer's post-ReLU outputs per ensemble member, real rows only.
+// act_stats: score[z * s_score + j] = s_j = mean_b |H[z][b][j]| (column sums in fp64: one partial per row
+// chunk in part [Z][act_stats_chunks(M)][W], added in order), norm[z * s_norm + j] = s_j / (mean_j s_j + 1e-9),
+// count[z * s_count] = #(norm <= threshold).  Deterministic (no float atomics).
+struct ActStats {
+  const float* H;
+  int Z, M, W, ld;
+  long long sH;
+  float threshold;
+  double* part;
+  float* score;
+  long long s_score;
+  float* norm;
+  long long s_norm;
+  int* count;
+  int s_count;
+};
+int act_stats_chunks(int M);
+void act_stats(const ActStats& s, hipStream_t st);
+// act_gram: gram[z * sG] = H[z]^T H[z] (W x W) when W <= M, else H[z] H[z]^T (M x M), dense [r][r] with
+// r = act_gram_dim(M, W) = min(M, W), fp64 on v_mfma_f64_16x16x4_f64 (the fp32 inputs widened on load: exact
+// products, fp64 sums in one fixed order), the upper triangle's tiles computed and mirrored.
+struct ActGram {
+  const float* H;
+  int Z, M, W, ld;
+  long long sH;
+  double* gram;
+  long long sG;
+};
+int act_gram_dim(int M, int W);
+void act_gram(const ActGram& g, hipStream_t st);
+
 // sets what mtsac_last_error returns on this thread (engine.cpp; the debug entry points name a
 // written guard band through it)
 void set_last_error(const char* msg);

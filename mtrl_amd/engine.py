@@ -252,6 +252,47 @@ class MTSACEngine:
         return {"gram": gram, "l1": l1, "conflict": counts[0], "intersection": counts[1], "genuine": counts[2],
                 "mismatch": counts[3], "near_zero": nz}
 
+    # ------------------------------------------------------------------ network health metrics
+    def network_metrics(self, observations=None, eps=None, dormant: bool = True, gram: bool = True,
+                        threshold: float = 0.1) -> dict:
+        """Dormant-neuron statistics and activation Grams of every trunk layer (include/mtsac.h,
+        mtsac_network_metrics), nothing updated.  ``observations`` [B][obs_dim] (rows interleaved i*T + t) or
+        None (a device sample); ``eps`` [B][A] or None (device noise).  Returns ``{"actor": r, "critic": r}`` with
+        ``r = {"members": E, "depth": D, "width": W, "scores": [E][D][W] float32 normalised scores,
+        "counts": [E][D] int32, "gram": E lists of D float64 [r][r] matrices}`` (the parts not asked for: None).
+        mtrl_amd/netmetrics.py makes the LogDict of them."""
+        c = self.config
+        what = (1 if dormant else 0) | (2 if gram else 0)
+        bp, keep = None, None
+        if observations is not None:
+            keep = _ptr(observations)
+            b = Batch(keep[0], None, None, None, None)
+            bp = ctypes.byref(b)
+        ep = _ptr(eps)
+        check(self.lib.mtsac_network_metrics(self._h, bp, ep[0] or None, what, float(threshold)))
+        out = {}
+        for which, (name, W, D, E) in enumerate((("actor", c.actor_width, c.actor_depth, 1),
+                                                 ("critic", c.critic_width, c.critic_depth, c.num_critics))):
+            r = {"members": E, "depth": D, "width": W, "scores": None, "counts": None, "gram": None}
+            if dormant:
+                r["scores"], r["counts"] = np.empty((E, D, W), np.float32), np.empty((E, D), np.int32)
+                check(self.lib.mtsac_get_network_scores(self._h, which, r["scores"].ctypes.data,
+                                                        r["counts"].ctypes.data))
+            if gram:
+                n = check(self.lib.mtsac_network_gram_dim(self._h, which))
+                r["gram"] = [[np.empty((n, n), np.float64) for _ in range(D)] for _ in range(E)]
+                for e in range(E):
+                    for i in range(D):
+                        check(self.lib.mtsac_get_network_gram(self._h, which, e, i, r["gram"][e][i].ctypes.data))
+            out[name] = r
+        return out
+
+    def network_metrics_kernel_ms(self) -> tuple[float, float]:
+        """HIP-event time of the last network_metrics call's statistics and Gram kernels (ms)."""
+        ms = (ctypes.c_double * 2)()
+        check(self.lib.mtsac_debug_network_metrics_ms(self._h, ms))
+        return float(ms[0]), float(ms[1])
+
     # ------------------------------------------------------------------ PCGrad (include/mtsac.h)
     def set_pcgrad(self, on: bool, cosine_sim_logs: bool = False) -> None:
         """PCGrad on both optimizers: update / update_many run the gradient-surgery step."""
