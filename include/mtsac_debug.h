@@ -156,6 +156,14 @@ int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, i
                             const float* Wh, const float* bh, const float* eps, float ls_min, float ls_max,
                             float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,
                             int* rows);
+/* The same launch with eps == NULL in PolicyParams: the heads draw their noise from the device stream,
+ * normal4(seed, stream + 16 (lane >> 2), counter, noise_div > 0 ? b / noise_div : b)[lane & 3] for action lane
+ * `lane` of row b (devrng.h), stream = stream_id for the first row set and stream_id + 1 for the second of form 2;
+ * counter is copied to the device word the heads read.  The drawn noise comes back in cache[:, 4A:5A]. */
+int mtsac_debug_head_policy_noise(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task,
+                                  const float* h, const float* Wh, const float* bh, uint64_t seed, uint32_t stream_id,
+                                  uint64_t counter, int noise_div, float ls_min, float ls_max, float* a_out,
+                                  float* a_out2, float* logpi, float* cache, float* planes, int* counts, int* rows);
 /* critic_head: mode 0 target, 1 critic, 2 actor; flags bit 0 fused_target (mode 1: th / tWh / tbh the target
  * critic's head inputs, y_out written), bit 1 clip.  h [E][B][W], Wh [E][T_l][W], bh [E][T_l], log_alpha
  * [T_glob], y [B] (mode 1 without fused_target), tw [B] or null.  Outputs y_out, row_a, row_b, alpha_w [B],
@@ -232,6 +240,42 @@ int mtsac_debug_wgrad_finish(int mode, int E, int M, int N, int K, int chunks, i
  * rest NaN), out2: db [batch][cols]. */
 int mtsac_debug_layout(int kind, const int* dims, const float* x, void* out, void* out2);
 
+/* The replay kernels (replay.hip) one launch at a time: device 0, null stream, host pointers in and out, outputs
+ * guarded as the head entries' are (an element left alone comes back NaN / -1 / all-ones words, a written band
+ * returns -5 and names the buffer); -22 for bad sizes or an index / task id out of range, before anything is
+ * launched.  Tests only.
+ *
+ * The index stream.  state [6] in and out: the PcgDev words state_hi, state_lo, inc_hi, inc_lo, has_uint32,
+ * uinteger.  mode 0: replay_indices_high with high = high_or_size; mode 1: replay_indices with *buf_size =
+ * high_or_size on the device (high = max(size, n)).  The jump table is pcg_jump_table's, as in the engines.
+ * idx [n_alloc], n_alloc >= n: positions >= n must come back -1.  -22 for high >= 2^31. */
+int mtsac_debug_replay_indices(uint64_t* state, int mode, int64_t high_or_size, int n, int n_alloc, int32_t* idx);
+/* replay_gather (dims[0] = 0: store [cap][T_l][R] and idx [n], B = n T_l rows) or batch_scatter (dims[0] = 1: the
+ * five user arrays of B = n rows, row b of local task b % T_l).  dims [17] = source, n, T_l, cap, obs_dim D,
+ * act_dim A, T_glob, task_begin, ld_a, ld_c, plane mode (0 none, 1 split3, 2 split2h with *in_max), pa_ld, pc_ld,
+ * pa_next, rows allocated per pa plane, rows allocated per pc / pcn / pcp plane, R.  rmin / rmax [T_l] (both or
+ * neither) with norm_eps: the gather's reward normalisation.  Outputs xa, xa_next [B][ld_a], xc, xc_next, xc_pi
+ * [B][ld_c], rew, done, task [B], err [1] (starts 0); with planes the raw 16-bit words of pa [np][pa rows][pa_ld]
+ * and pc, pcn, pcp [np][pc rows][pc_ld] (np = 3, split2h 2) and *in_rec_e = in_rec->e (split2h). */
+int mtsac_debug_replay_gather(const int* dims, const float* store, const int32_t* idx, const float* u_obs,
+                              const float* u_act, const float* u_nobs, const float* u_done, const float* u_rew,
+                              const double* rmin, const double* rmax, double norm_eps, const float* in_max, float* xa,
+                              float* xa_next, float* xc, float* xc_next, float* xc_pi, float* rew, float* done,
+                              int32_t* task, int32_t* err, uint16_t* pa, uint16_t* pc, uint16_t* pcn, uint16_t* pcp,
+                              int32_t* in_rec_e);
+/* task_rows: task [B] (ids < T_l <= 64) -> counts [T_l], rows [T_l][max_rows] (-1 past min(counts[t], max_rows)). */
+int mtsac_debug_task_rows(int B, int T_l, int max_rows, const int32_t* task, int32_t* counts, int32_t* rows);
+/* buffer_pack_slot then buffer_commit_slot of one slot: obs, nobs [T_l][D], act [T_l][A], rew, done [T_l] -> rec
+ * [T_l][R]; rmin / rmax [T_l] in and out (both or neither), *buf_size = size out, *bufmax in and out (nullable). */
+int mtsac_debug_pack_commit(int T_l, int D, int A, int R, int64_t size, const float* obs, const float* nobs,
+                            const float* act, const float* rew, const float* done, float* rec, double* rmin,
+                            double* rmax, int64_t* buf_size, float* bufmax);
+/* absmax_into: *m = max(*m, max |x[0..n)|), *m in and out. */
+int mtsac_debug_absmax(int64_t n, const float* x, float* m);
+/* fill_synthetic: store [cap][T_l][R], R = round_up(2 D + A + 2, 4), and *bufmax in and out. */
+int mtsac_debug_fill_synthetic(int64_t cap, int T_l, int D, int A, int T_glob, int task_begin, uint64_t seed,
+                               float* store, float* bufmax);
+
 /* Eager update_many overlaps consecutive steps (the next gather and critic(s, a) forward beside
  * the previous actor backward / all-reduce / Adam): on = 1 always, 0 never (whole steps), -1 the
  * default (when the trunk gradients go through a device collective: RCCL or the modelled one).
@@ -255,7 +299,9 @@ int mtsac_debug_opt_form(struct mtsac_engine* engine, int which);
 int mtsac_debug_check_guards(struct mtsac_engine* engine);
 /* Step buffer views (diagnostics): snapshot on/off; read id 0 actor top activations, 1 / 2 their
  * snapshots after the actor forward / the actor-loss pass ([Ma][W]), 3 actor dout ([B][2A]), 4 actor
- * gradient head leaves.  count must equal the buffer's float count. */
+ * gradient head leaves, 5 the actor-loss pass's policy cache of the last step ([B][5A]: mu, ls, x, a, eps; the
+ * actor backward reads it and nothing writes it again before the next step).  count must equal the buffer's
+ * float count. */
 int mtsac_debug_snapshot(struct mtsac_engine* engine, int32_t on);
 int mtsac_debug_read(struct mtsac_engine* engine, int32_t id, float* dst, int64_t count);
 /* the head backward's LDS self-check, tested: the last step's actor head weight pass re-run into a

@@ -193,6 +193,14 @@ SIGNATURES = {
     "mtsac_debug_head_rw": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_head_bwd_split": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_head_policy": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 5 + [ctypes.c_float] * 2 + [P] * 7),
+    "mtsac_debug_head_policy_noise": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 4 + [U64, U32, U64, ctypes.c_int] +
+                                      [ctypes.c_float] * 2 + [P] * 7),
+    "mtsac_debug_replay_indices": (ctypes.c_int, [P, ctypes.c_int, I64, ctypes.c_int, ctypes.c_int, P]),
+    "mtsac_debug_replay_gather": (ctypes.c_int, [P] * 10 + [ctypes.c_double] + [P] * 15),
+    "mtsac_debug_task_rows": (ctypes.c_int, [ctypes.c_int] * 3 + [P] * 3),
+    "mtsac_debug_pack_commit": (ctypes.c_int, [ctypes.c_int] * 4 + [I64] + [P] * 10),
+    "mtsac_debug_absmax": (ctypes.c_int, [I64, P, P]),
+    "mtsac_debug_fill_synthetic": (ctypes.c_int, [I64] + [ctypes.c_int] * 5 + [U64, P, P]),
     "mtsac_debug_head_critic": (ctypes.c_int, [ctypes.c_int] * 8 + [P] * 13 + [ctypes.c_float] * 2 + [P] * 7),
     "mtsac_debug_head_active_rows": (ctypes.c_int, [ctypes.c_int] * 2 + [P] * 4),
     "mtsac_debug_head_backward": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 14),

@@ -138,6 +138,14 @@ struct Guarded {
   }
 };
 
+// a guarded buffer that starts as the host's n values (in and out)
+template <typename T>
+T* guarded_inout(Guarded& g, const T* host, size_t n, const char* name) {
+  T* d = g.out<T>(n, name);
+  if (d && hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) g.ok = false;
+  return d;
+}
+
 int sync_rc(const char* what) {
   const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize();
   if (e1 == hipSuccess && e2 == hipSuccess) return 0;
@@ -962,13 +970,15 @@ int mtsac_debug_head_bwd_split(int mode) {
   return old;
 }
 
-int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
-                            const float* Wh, const float* bh, const float* eps, float ls_min, float ls_max,
-                            float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,
-                            int* rows) {
+// eps given: injected noise; eps null: the device stream (seed, stream_id + s for row set s, counter, noise_div)
+static int head_policy_run(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
+                           const float* Wh, const float* bh, const float* eps, unsigned long long seed,
+                           unsigned int stream_id, unsigned long long counter, int noise_div, float ls_min,
+                           float ls_max, float* a_out, float* a_out2, float* logpi, float* cache, float* planes,
+                           int* counts, int* rows) {
   const bool whT = flags & 1, p3 = flags & 2, p2h = flags & 4;
   if (form < 0 || form > 2 || (flags & ~7) || (p3 && p2h) || W < 1 || A < 1 || A > 64 || !head_kernels_cover(2 * A, W) || ld_a < A || !h || !Wh || !bh ||
-      !eps || !a_out || !a_out2 || !logpi || !cache || !counts || !rows || ((p3 || p2h) && !planes) ||
+      noise_div < 0 || !a_out || !a_out2 || !logpi || !cache || !counts || !rows || ((p3 || p2h) && !planes) ||
       !tasks_ok(task, B, T_l) || (long long)B * W >= (1LL << 28) ||
       !outputs_distinct({a_out, a_out2, logpi, cache, planes, counts, rows}))
     return -22;
@@ -979,6 +989,7 @@ int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, i
   TaskLists tl = make_lists(g, task, B, T_l);
   const float *d_h = g.in(h, (size_t)ns * B * W), *d_Wh = g.in(Wh, nw), *d_bh = g.in(bh, (size_t)T_l * hd);
   const float* d_eps = g.in(eps, (size_t)ns * B * A);
+  const unsigned long long* d_counter = g.in(&counter, 1);
   float* d_WhT = whT ? g.out<float>(nw, "WhT") : nullptr;
   PlaneRec* rec = p2h ? rec_out(g, H2E, "ap_rec") : nullptr;
   float *d_a[2], *d_a2[2], *d_lp[2], *d_c[2];
@@ -997,7 +1008,8 @@ int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, i
     PolicyParams p{};
     p.head.h = d_h + (size_t)s * B * W; p.head.Wh = d_Wh; p.head.WhT = d_WhT; p.head.bh = d_bh; p.head.task = tl.d_task;
     p.head.B = B; p.head.W = W; p.head.hd = hd; p.head.E = 1;
-    p.eps = d_eps + (size_t)s * B * A;
+    p.eps = d_eps ? d_eps + (size_t)s * B * A : nullptr;
+    p.seed = seed; p.counter = d_counter; p.stream_id = stream_id + (unsigned)s; p.noise_div = noise_div;
     p.A = A; p.ls_min = ls_min; p.ls_max = ls_max;
     p.a_out = d_a[s]; p.ld_a_out = ld_a; p.a_out2 = d_a2[s]; p.ld_a_out2 = ld_a;
     p.a_planes = d_pl[s]; p.ap_ps = (long long)B * ld_a; p.ap_ld = ld_a; p.ap_rec = rec;
@@ -1019,6 +1031,23 @@ int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, i
       return -5;
   }
   return g.back(counts, tl.counts, (size_t)T_l) && g.back(rows, tl.rows, (size_t)T_l * B) ? 0 : -5;
+}
+
+int mtsac_debug_head_policy(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
+                            const float* Wh, const float* bh, const float* eps, float ls_min, float ls_max,
+                            float* a_out, float* a_out2, float* logpi, float* cache, float* planes, int* counts,
+                            int* rows) {
+  if (!eps) return -22;
+  return head_policy_run(form, flags, B, T_l, W, A, ld_a, task, h, Wh, bh, eps, 0ull, 0u, 0ull, 0, ls_min, ls_max, a_out,
+                         a_out2, logpi, cache, planes, counts, rows);
+}
+
+int mtsac_debug_head_policy_noise(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task,
+                                  const float* h, const float* Wh, const float* bh, uint64_t seed, uint32_t stream_id,
+                                  uint64_t counter, int noise_div, float ls_min, float ls_max, float* a_out,
+                                  float* a_out2, float* logpi, float* cache, float* planes, int* counts, int* rows) {
+  return head_policy_run(form, flags, B, T_l, W, A, ld_a, task, h, Wh, bh, nullptr, seed, stream_id, counter, noise_div,
+                         ls_min, ls_max, a_out, a_out2, logpi, cache, planes, counts, rows);
 }
 
 int mtsac_debug_head_critic(int mode, int flags, int B, int T_l, int E, int W, int T_glob, int task_begin,
@@ -1584,6 +1613,189 @@ int mtsac_debug_layout(int kind, const int* dims, const float* x, void* out, voi
                  gd.back(reinterpret_cast<float*>(out2), d_db, (size_t)batch * cols)
              ? 0
              : -5;
+}
+
+// ---- the replay kernels (replay.hip) ----
+extern int pcg_jump_table(unsigned long long* out);  // engine.cpp: 65 x (A_hi, A_lo, C_hi, C_lo)
+
+int mtsac_debug_replay_indices(uint64_t* state, int mode, int64_t high_or_size, int n, int n_alloc, int32_t* idx) {
+  if (!state || !idx || (mode != 0 && mode != 1) || n < 1 || n_alloc < n || n_alloc > (1 << 24) || high_or_size < 1 ||
+      high_or_size >= (1LL << 31) || (state[4] & ~1ull) || state[5] > 0xFFFFFFFFull)
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  unsigned long long jt[65 * 4];
+  pcg_jump_table(jt);
+  PcgDev s{state[0], state[1], state[2], state[3], (int)state[4], (unsigned)state[5]};
+  const long long size = high_or_size;
+  Guarded g;
+  const unsigned long long* d_jump = g.in(jt, (size_t)65 * 4);
+  const long long* d_size = g.in(&size, 1);
+  PcgDev* d_rng = guarded_inout(g, &s, 1, "rng");
+  int* d_idx = g.out<int>((size_t)n_alloc, "idx");
+  if (!g.ok) return -12;
+  if (mode == 0) replay_indices_high(d_rng, d_jump, size, n, d_idx, nullptr);
+  else replay_indices(d_rng, d_jump, d_size, n, d_idx, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("replay_indices")) || (rc = g.check())) return rc;
+  if (!g.back(&s, d_rng, 1) || !g.back(idx, d_idx, (size_t)n_alloc)) return -5;
+  state[0] = s.state_hi; state[1] = s.state_lo; state[2] = s.inc_hi; state[3] = s.inc_lo;
+  state[4] = (uint64_t)(unsigned)s.has_uint32; state[5] = s.uinteger;
+  return 0;
+}
+
+int mtsac_debug_replay_gather(const int* dims, const float* store, const int32_t* idx, const float* u_obs,
+                              const float* u_act, const float* u_nobs, const float* u_done, const float* u_rew,
+                              const double* rmin, const double* rmax, double norm_eps, const float* in_max, float* xa,
+                              float* xa_next, float* xc, float* xc_next, float* xc_pi, float* rew, float* done,
+                              int32_t* task, int32_t* err, uint16_t* pa, uint16_t* pc, uint16_t* pcn, uint16_t* pcp,
+                              int32_t* in_rec_e) {
+  if (!dims) return -22;
+  const int src = dims[0], n = dims[1], T_l = dims[2], cap = dims[3], D = dims[4], A = dims[5], T_glob = dims[6],
+            task_begin = dims[7], ld_a = dims[8], ld_c = dims[9], pm = dims[10], pa_ld = dims[11], pc_ld = dims[12],
+            pa_next = dims[13], pa_rows = dims[14], pc_rows = dims[15], R = dims[16];
+  if ((src != 0 && src != 1) || n < 1 || T_l < 1 || T_l > 64 || D < 1 || A < 1 || A > 64 || T_glob < 1 || T_glob > D ||
+      task_begin < 0 || ld_a < D || ld_c < A + D || R < 2 * D + A + 2 || pm < 0 || pm > 2 || (long long)n * T_l > (1 << 20) ||
+      !xa || !xa_next || !xc || !xc_next || !xc_pi || !rew || !done || !task || !err || (rmin == nullptr) != (rmax == nullptr))
+    return -22;
+  const int B = src == 0 ? n * T_l : n;
+  if (src == 0) {
+    if (!store || !idx || cap < 1 || (long long)cap * T_l * R >= (1LL << 27)) return -22;
+    for (int i = 0; i < n; ++i)
+      if (idx[i] < 0 || idx[i] >= cap) return -22;
+  } else if (!u_obs || !u_act || !u_nobs || !u_done || !u_rew) {
+    return -22;
+  }
+  if (pm && (!pa || !pc || !pcn || !pcp || pa_ld < D || pc_ld < A + D || pa_next < 0 || pa_rows < pa_next + B || pc_rows < B ||
+             (pm == 2 && (!in_max || !in_rec_e))))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  GatherParams p{};
+  p.store = src == 0 ? g.in(store, (size_t)cap * T_l * R) : nullptr;
+  p.idx = src == 0 ? g.in(idx, (size_t)n) : nullptr;
+  p.n = n; p.T_l = T_l; p.R = R; p.obs_dim = D; p.act_dim = A; p.T_glob = T_glob; p.task_begin = task_begin;
+  p.ld_a = ld_a; p.ld_c = ld_c;
+  p.xa = g.out<float>((size_t)B * ld_a, "xa");
+  p.xa_next = g.out<float>((size_t)B * ld_a, "xa_next");
+  p.xc = g.out<float>((size_t)B * ld_c, "xc");
+  p.xc_next = g.out<float>((size_t)B * ld_c, "xc_next");
+  p.xc_pi = g.out<float>((size_t)B * ld_c, "xc_pi");
+  p.rew = g.out<float>((size_t)B, "rew");
+  p.done = g.out<float>((size_t)B, "done");
+  p.task = g.out<int>((size_t)B, "task");
+  p.err = g.out<int>(1, "err");
+  if (p.err && hipMemset(p.err, 0, sizeof(int)) != hipSuccess) g.ok = false;
+  p.rmin = g.in(rmin, (size_t)T_l);
+  p.rmax = g.in(rmax, (size_t)T_l);
+  p.norm_eps = norm_eps;
+  const int np = pm == 2 ? 2 : 3;
+  const size_t pa_ps = (size_t)pa_rows * pa_ld, pc_ps = (size_t)pc_rows * pc_ld;
+  PlaneRec* rec = nullptr;
+  if (pm) {
+    p.pa = g.out<__bf16>(np * pa_ps, "pa");
+    p.pc = g.out<__bf16>(np * pc_ps, "pc");
+    p.pcn = g.out<__bf16>(np * pc_ps, "pcn");
+    p.pcp = g.out<__bf16>(np * pc_ps, "pcp");
+    p.pa_ps = (long long)pa_ps; p.pa_next = pa_next; p.pa_ld = pa_ld; p.pc_ps = (long long)pc_ps; p.pc_ld = pc_ld;
+    if (pm == 2) {
+      rec = g.out<PlaneRec>(1, "in_rec");
+      p.in_rec = rec;
+      p.in_max = g.in(in_max, 1);
+    }
+  }
+  const float *d_o = nullptr, *d_a = nullptr, *d_no = nullptr, *d_d = nullptr, *d_r = nullptr;
+  if (src == 1) {
+    d_o = g.in(u_obs, (size_t)B * D); d_a = g.in(u_act, (size_t)B * A); d_no = g.in(u_nobs, (size_t)B * D);
+    d_d = g.in(u_done, (size_t)B); d_r = g.in(u_rew, (size_t)B);
+  }
+  if (!g.ok) return -12;
+  if (src == 0) replay_gather(p, nullptr);
+  else batch_scatter(p, d_o, d_a, d_no, d_d, d_r, B, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("gather")) || (rc = g.check())) return rc;
+  bool ok = g.back(xa, p.xa, (size_t)B * ld_a) && g.back(xa_next, p.xa_next, (size_t)B * ld_a) &&
+            g.back(xc, p.xc, (size_t)B * ld_c) && g.back(xc_next, p.xc_next, (size_t)B * ld_c) &&
+            g.back(xc_pi, p.xc_pi, (size_t)B * ld_c) && g.back(rew, p.rew, (size_t)B) && g.back(done, p.done, (size_t)B) &&
+            g.back(task, p.task, (size_t)B) && g.back(err, p.err, 1);
+  if (ok && pm)
+    ok = g.back(reinterpret_cast<__bf16*>(pa), p.pa, np * pa_ps) && g.back(reinterpret_cast<__bf16*>(pc), p.pc, np * pc_ps) &&
+         g.back(reinterpret_cast<__bf16*>(pcn), p.pcn, np * pc_ps) && g.back(reinterpret_cast<__bf16*>(pcp), p.pcp, np * pc_ps);
+  if (ok && rec) ok = g.back(in_rec_e, &rec->e, 1);
+  return ok ? 0 : -5;
+}
+
+int mtsac_debug_task_rows(int B, int T_l, int max_rows, const int32_t* task, int32_t* counts, int32_t* rows) {
+  if (!tasks_ok(task, B, T_l) || max_rows < 1 || !counts || !rows || (long long)T_l * max_rows > (1 << 24)) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  const int* d_task = g.in(task, (size_t)B);
+  int* d_counts = g.out<int>((size_t)T_l, "counts");
+  int* d_rows = g.out<int>((size_t)T_l * max_rows, "rows");
+  if (!g.ok) return -12;
+  task_rows(d_task, B, T_l, d_counts, d_rows, max_rows, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("task_rows")) || (rc = g.check())) return rc;
+  return g.back(counts, d_counts, (size_t)T_l) && g.back(rows, d_rows, (size_t)T_l * max_rows) ? 0 : -5;
+}
+
+int mtsac_debug_pack_commit(int T_l, int D, int A, int R, int64_t size, const float* obs, const float* nobs,
+                            const float* act, const float* rew, const float* done, float* rec, double* rmin,
+                            double* rmax, int64_t* buf_size, float* bufmax) {
+  if (T_l < 1 || T_l > 64 || D < 1 || A < 1 || R < 2 * D + A + 2 || (long long)T_l * R > (1 << 24) || !obs || !nobs || !act ||
+      !rew || !done || !rec || !buf_size || (rmin == nullptr) != (rmax == nullptr))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  const float *d_o = g.in(obs, (size_t)T_l * D), *d_no = g.in(nobs, (size_t)T_l * D), *d_a = g.in(act, (size_t)T_l * A);
+  const float *d_r = g.in(rew, (size_t)T_l), *d_d = g.in(done, (size_t)T_l);
+  float* d_rec = g.out<float>((size_t)T_l * R, "rec");
+  double* d_min = rmin ? guarded_inout(g, rmin, (size_t)T_l, "rmin") : nullptr;
+  double* d_max = rmax ? guarded_inout(g, rmax, (size_t)T_l, "rmax") : nullptr;
+  long long* d_size = g.out<long long>(1, "buf_size");
+  float* d_bm = bufmax ? guarded_inout(g, bufmax, 1, "bufmax") : nullptr;
+  if (!g.ok) return -12;
+  buffer_pack_slot(d_rec, T_l, R, D, A, d_o, d_no, d_a, d_r, d_d, nullptr);
+  buffer_commit_slot(d_rec, T_l, R, D + A, d_min, d_max, d_size, (long long)size, nullptr, D, d_bm);
+  int rc = 0;
+  if ((rc = sync_rc("pack / commit slot")) || (rc = g.check())) return rc;
+  long long sz = 0;
+  bool ok = g.back(rec, d_rec, (size_t)T_l * R) && g.back(&sz, d_size, 1);
+  *buf_size = sz;
+  if (ok && rmin) ok = g.back(rmin, d_min, (size_t)T_l) && g.back(rmax, d_max, (size_t)T_l);
+  if (ok && bufmax) ok = g.back(bufmax, d_bm, 1);
+  return ok ? 0 : -5;
+}
+
+int mtsac_debug_absmax(int64_t n, const float* x, float* m) {
+  if (n < 1 || n > (1 << 26) || !x || !m) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  const float* d_x = g.in(x, (size_t)n);
+  float* d_m = guarded_inout(g, m, 1, "m");
+  if (!g.ok) return -12;
+  absmax_into(d_x, (long long)n, d_m, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("absmax_into")) || (rc = g.check())) return rc;
+  return g.back(m, d_m, 1) ? 0 : -5;
+}
+
+int mtsac_debug_fill_synthetic(int64_t cap, int T_l, int D, int A, int T_glob, int task_begin, uint64_t seed,
+                               float* store, float* bufmax) {
+  if (cap < 1 || T_l < 1 || D < 1 || A < 1 || T_glob < 1 || T_glob > D || task_begin < 0 || task_begin + T_l > T_glob ||
+      !store || !bufmax)
+    return -22;
+  const int R = (2 * D + A + 2 + 3) / 4 * 4;
+  if ((long long)cap * T_l * R > (1 << 26)) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  Guarded g;
+  const size_t nf = (size_t)cap * T_l * R;
+  float* d_store = g.out<float>(nf, "store");
+  float* d_bm = guarded_inout(g, bufmax, 1, "bufmax");
+  if (!g.ok) return -12;
+  fill_synthetic(d_store, (long long)cap, T_l, R, D, A, T_glob, task_begin, seed, nullptr, d_bm);
+  int rc = 0;
+  if ((rc = sync_rc("fill_synthetic")) || (rc = g.check())) return rc;
+  return g.back(store, d_store, nf) && g.back(bufmax, d_bm, 1) ? 0 : -5;
 }
 
 }  // extern "C"

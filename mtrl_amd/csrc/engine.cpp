@@ -4154,7 +4154,9 @@ int mtsac_debug_check_guards(mtsac_engine* h) {
 // Debug views of step buffers (tools/shard_diag.py).  mtsac_debug_snapshot(on): from the next step on,
 // copy the actor's top activations right after the actor forward and after the actor-loss pass.
 // mtsac_debug_read(id): 0 the actor's top activations now, 1 / 2 the two snapshots ([Ma][W] each),
-// 3 the actor head's output gradient dout ([B][2A]), 4 the actor gradient's head leaves.
+// 3 the actor head's output gradient dout ([B][2A]), 4 the actor gradient's head leaves, 5 the actor-loss
+// pass's policy cache ([B][5A]: mu, ls, x, a, eps), which the actor backward reads and nothing overwrites
+// until the next step's policy head.
 int mtsac_debug_snapshot(mtsac_engine* h, int32_t on) {
   if (!h) return fail(-22, "null engine");
   if (on && !h->dbg_snap[0])  // allocated once, reused when snapshots are turned on again (freed with the engine)
@@ -4190,6 +4192,7 @@ int mtsac_debug_read(mtsac_engine* h, int32_t id, float* dst, int64_t count) {
     case 2: src = h->dbg_snap[1]; n = (int64_t)h->Ma * h->actor.width; break;
     case 3: src = h->dout_a; n = (int64_t)h->B * 2 * h->A; break;
     case 4: src = h->actor.g; n = h->actor.trunk_off; break;
+    case 5: src = h->cache; n = (int64_t)h->B * 5 * h->A; break;
     default: return fail(-22, "unknown buffer id");
   }
   if (!src) return fail(-22, "buffer not allocated (mtsac_debug_snapshot)");

@@ -271,7 +271,8 @@ def test_update_many_draws_orders_on_device():
     np.testing.assert_equal(c.logs(), logs_a[1][0])
     np.testing.assert_equal(c.pcgrad_logs(), logs_a[1][1])
     # replay: engine b draws the same batch (mtsac_sample advances the same index stream); with the orders
-    # a drew and injected noise (device noise has no host counterpart) its step matches the oracle, and the
+    # a drew and injected noise (the oracle takes eps as an argument; the device stream has its own host model,
+    # tests/philox_ref.py, checked in test_gpu_noise_stream.py) its step matches the oracle, and the
     # noise-free log of a's own first step (qf_values = mean Q(s, a_data)) matches the oracle on that batch
     _, batch = b.sample()
     en = np.repeat(np.random.default_rng(3).standard_normal((n, 4)), T, axis=0).astype(np.float32)

@@ -170,7 +170,8 @@ def test_device_sampled_update_matches_oracle_with_same_indices():
         d = (rng.uniform(size=T) < 0.2).astype(np.float32)
         eng.buffer_add(o, no, a, r, d)
         orc.add(o, no, a, r, d)
-    # device noise cannot be matched, so draw the batch on both sides and inject eps via a user batch
+    # the oracle takes its noise as an argument (the device stream itself is held to its host model in
+    # test_gpu_noise_stream.py), so draw the batch on both sides and inject eps via a user batch
     idx, batch = eng.sample()
     want_idx = orc.sample_indices(n * T)
     np.testing.assert_array_equal(idx, want_idx)
