@@ -1,157 +1,13 @@
-// debug.cpp -- test-only entry points (include/mtsac_debug.h): the plane GEMMs, the DrQ kernels, the SAC heads.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <initializer_list>
-#include <string>
-#include <vector>
-
+// debug.cpp -- test-only entry points (include/mtsac_debug.h): the DrQ kernels, the SAC heads, the layout and
+// replay kernels, on debug_harness.h.  The GEMMs' entry points are in debug_gemm.cpp.
 #include "../../include/mtsac.h"
 #include "../../include/mtsac_debug.h"
+#include "debug_harness.h"
 #include "drq_kernels.h"
-#include "kernels.h"
 
 using namespace mtsac;
 
 namespace {
-
-long long up32(long long x) { return (x + 31) / 32 * 32; }
-
-__global__ void fill_rand_f32(float* p, long long n, unsigned seed) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned x = (unsigned)i * 2654435761u ^ seed;
-  x ^= x >> 13;
-  x *= 0x5bd1e995u;
-  x ^= x >> 15;
-  p[i] = ((float)(x & 0xFFFFFF) / 8388608.0f) - 1.0f;
-}
-
-struct DevBuf {
-  std::vector<void*> ptrs;
-  ~DevBuf() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-  template <typename T>
-  T* get(size_t n) {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) return nullptr;
-    (void)hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T));
-    ptrs.push_back(p);
-    return reinterpret_cast<T*>(p);
-  }
-};
-
-long long up8(long long x) { return (x + 7) / 8 * 8; }
-
-// planes of a fp32 operand stored [rows][K] (k contiguous) or, kmajor, [K][rows]; split in its
-// stored orientation: row-major planes [3][rows][up32(K)], k-major planes [3][up32(K)][up8(rows)]
-// (zeros in the padding)
-void plane_geom(int rows, int K, bool kmajor, long long& ld, long long& ps) {
-  ld = kmajor ? up8(rows) : up32(K);
-  ps = (kmajor ? up32(K) : (long long)rows) * ld;
-}
-
-void split_into(const float* dsrc, int rows, int K, bool kmajor, __bf16* out, const int* e2h = nullptr,
-                bool frag = false) {
-  long long ld, ps;
-  plane_geom(rows, K, kmajor, ld, ps);
-  SplitParams s{};
-  s.x = dsrc;
-  s.ldx = kmajor ? rows : K;
-  s.rows = kmajor ? K : rows;
-  s.cols = kmajor ? rows : K;
-  s.out_rows = kmajor ? (int)up32(K) : rows;
-  s.out = out;
-  s.ldo = ld;
-  s.po = ps;
-  s.out_cols = (int)ld;
-  s.e2h = e2h;
-  s.frag = frag ? 1 : 0;
-  split_planes(s, false, 1, nullptr);
-}
-
-__bf16* make_planes(DevBuf& db, const float* dsrc, int rows, int K, bool kmajor, long long& ld, long long& ps) {
-  plane_geom(rows, K, kmajor, ld, ps);
-  __bf16* out = db.get<__bf16>(3 * ps);
-  if (out) split_into(dsrc, rows, K, kmajor, out);
-  return out;
-}
-
-// Device buffers of the single-kernel DrQ entry points.  An output lies between two 256-byte bands
-// of GUARD_BYTE and starts as all-ones words (NaN as float, -1 as int, 255 as byte), so a store
-// outside it and an element the kernel left alone both show; the bands only detect.
-constexpr size_t GUARD = 256;
-constexpr int GUARD_BYTE = 0xA5;
-struct Guarded {
-  DevBuf mem;
-  struct Out {
-    unsigned char* raw;
-    size_t bytes;
-    const char* name;
-  };
-  std::vector<Out> outs;
-  bool ok = true;
-  template <typename T>
-  T* in(const T* host, size_t n) {  // null host: no buffer
-    if (!host) return nullptr;
-    T* d = mem.get<T>(n);
-    if (!d || hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-    return d;
-  }
-  template <typename T>
-  T* out(size_t n, const char* name) {
-    const size_t bytes = n * sizeof(T);
-    unsigned char* raw = mem.get<unsigned char>(bytes + 2 * GUARD);
-    if (!raw || hipMemset(raw, GUARD_BYTE, bytes + 2 * GUARD) != hipSuccess ||
-        hipMemset(raw + GUARD, 0xFF, bytes) != hipSuccess) {
-      ok = false;
-      return nullptr;
-    }
-    outs.push_back({raw, bytes, name});
-    return reinterpret_cast<T*>(raw + GUARD);
-  }
-  // 0, or -5 with the first written band named in mtsac_last_error
-  int check() {
-    unsigned char band[2 * GUARD];
-    for (const Out& o : outs) {
-      if (hipMemcpy(band, o.raw, GUARD, hipMemcpyDeviceToHost) != hipSuccess ||
-          hipMemcpy(band + GUARD, o.raw + GUARD + o.bytes, GUARD, hipMemcpyDeviceToHost) != hipSuccess)
-        return -5;
-      for (size_t i = 0; i < 2 * GUARD; ++i)
-        if (band[i] != GUARD_BYTE) {
-          char msg[160];
-          snprintf(msg, sizeof msg, "guard band written: buffer %s, %s band, byte %d", o.name,
-                   i < GUARD ? "leading" : "trailing", (int)(i % GUARD));
-          set_last_error(msg);
-          return -5;
-        }
-    }
-    return 0;
-  }
-  template <typename T>
-  bool back(T* host, const T* dev, size_t n) {
-    return hipMemcpy(host, dev, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
-  }
-};
-
-// a guarded buffer that starts as the host's n values (in and out)
-template <typename T>
-T* guarded_inout(Guarded& g, const T* host, size_t n, const char* name) {
-  T* d = g.out<T>(n, name);
-  if (d && hipMemcpy(d, host, n * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) g.ok = false;
-  return d;
-}
-
-int sync_rc(const char* what) {
-  const hipError_t e1 = hipGetLastError(), e2 = hipDeviceSynchronize();
-  if (e1 == hipSuccess && e2 == hipSuccess) return 0;
-  set_last_error((std::string(what) + ": " + hipGetErrorString(e1 != hipSuccess ? e1 : e2)).c_str());
-  return -5;
-}
 
 // ---- single SAC head kernels (heads.hip) ----
 // counts / rows of task[B] from task_rows on the device (row stride B), both guarded outputs
@@ -165,14 +21,6 @@ bool tasks_ok(const int* task, int B, int T_l) {
   if (!task || B < 1 || T_l < 1 || T_l > 64) return false;
   for (int b = 0; b < B; ++b)
     if (task[b] < 0 || task[b] >= T_l) return false;
-  return true;
-}
-// host output buffers of one call must not share a start address: each is copied back over whatever the
-// one before it left there, so the caller would read one output under another's name (null entries skipped)
-bool outputs_distinct(std::initializer_list<const void*> outs) {
-  for (auto a = outs.begin(); a != outs.end(); ++a)
-    for (auto b = a + 1; b != outs.end(); ++b)
-      if (*a != nullptr && *a == *b) return false;
   return true;
 }
 TaskLists make_lists(Guarded& g, const int* task, int B, int T_l) {
@@ -191,610 +39,10 @@ PlaneRec* rec_out(Guarded& g, int e, const char* name) {
   if (r && hipMemcpy(&r->e, &e, sizeof(int), hipMemcpyHostToDevice) != hipSuccess) g.ok = false;
   return r;
 }
-// the unscaled sum of n elements' planes (16-bit words, plane stride ps): split3 h + m + l, split2h (h + l) 2^-e
-bool planes_sum(const __bf16* dev, size_t n_words, size_t ps, size_t n, bool h2, int e, float* out) {
-  std::vector<unsigned short> w(n_words);
-  if (hipMemcpy(w.data(), dev, n_words * 2, hipMemcpyDeviceToHost) != hipSuccess) return false;
-  for (size_t i = 0; i < n; ++i) {
-    if (h2) {
-      _Float16 a, b;
-      std::memcpy(&a, &w[i], 2);
-      std::memcpy(&b, &w[ps + i], 2);
-      out[i] = std::ldexp((float)a + (float)b, -e);
-    } else {
-      __bf16 a, b, c;
-      std::memcpy(&a, &w[i], 2);
-      std::memcpy(&b, &w[ps + i], 2);
-      std::memcpy(&c, &w[2 * ps + i], 2);
-      out[i] = ((float)a + (float)b) + (float)c;
-    }
-  }
-  return true;
-}
-
-// split2h test records: max |x| and the plane exponent of that bound, as plane_exp (gemm_common.h) gives it
-float host_amax(const float* x, size_t n) {
-  float m = 0.f;
-  for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(x[i]));
-  return m;
-}
-int host_plane_exp(float b) {
-  b *= 1.00390625f;
-  if (!(b > 0.f)) return 0;
-  int ex;
-  (void)std::frexp(b, &ex);
-  return 15 - ex;
-}
 
 }  // namespace
 
 extern "C" {
-
-int mtsac_debug_gemm_x3p(int epi, int M, int N, int K, const float* A, int a_kmajor, const float* B, int b_kmajor,
-                         float* C, const float* bias, const float* mask, float* Csum) {
-  const int splits = (epi >> 8) & 255;
-  epi &= 255;
-  if (M < 1 || N < 1 || K < 1 || !A || !B || !C) return -22;
-  DevBuf d;
-  float* dA = d.get<float>((size_t)M * K);
-  float* dB = d.get<float>((size_t)N * K);
-  float* dC = d.get<float>((size_t)M * N);
-  float* dbias = d.get<float>(N);
-  float* dmask = d.get<float>((size_t)M * N);
-  __bf16* dCp = d.get<__bf16>((size_t)3 * M * N);
-  float* dws = d.get<float>(splits > 1 ? (size_t)gemm_ws_floats(M, N, 1, splits) : 1);
-  if (!dA || !dB || !dC || !dbias || !dmask || !dCp || !dws) return -12;
-  (void)hipMemcpy(dA, A, sizeof(float) * M * K, hipMemcpyHostToDevice);
-  (void)hipMemcpy(dB, B, sizeof(float) * N * K, hipMemcpyHostToDevice);
-  if (bias) (void)hipMemcpy(dbias, bias, sizeof(float) * N, hipMemcpyHostToDevice);
-  if (mask) (void)hipMemcpy(dmask, mask, sizeof(float) * M * N, hipMemcpyHostToDevice);
-  long long lda, pa, ldb, pb;
-  __bf16* Ap = make_planes(d, dA, M, K, a_kmajor != 0, lda, pa);
-  __bf16* Bp = make_planes(d, dB, N, K, b_kmajor != 0, ldb, pb);
-  if (!Ap || !Bp) return -12;
-  SplitGemmParams g{};
-  g.A = Ap; g.lda = lda; g.pA = pa; g.a_kmajor = a_kmajor != 0;
-  g.B = Bp; g.ldb = ldb; g.pB = pb; g.b_kmajor = b_kmajor != 0;
-  g.C = dC; g.ldc = N;
-  g.bias = dbias;
-  g.mask = dmask; g.ldm = N;
-  if (Csum) {
-    g.Cp = dCp; g.ldcp = N; g.pC = (long long)M * N;
-  }
-  g.M = M; g.N = N; g.K = (int)up32(K);
-  g.splits = splits;
-  g.ws = dws;
-  gemm_x3p(g, epi, 1, nullptr);
-  if (hipDeviceSynchronize() != hipSuccess) return -5;
-  if (hipMemcpy(C, dC, sizeof(float) * M * N, hipMemcpyDeviceToHost) != hipSuccess) return -5;
-  if (Csum) {
-    std::vector<__bf16> h((size_t)3 * M * N);
-    if (hipMemcpy(h.data(), dCp, sizeof(__bf16) * h.size(), hipMemcpyDeviceToHost) != hipSuccess) return -5;
-    const size_t n = (size_t)M * N;
-    for (size_t i = 0; i < n; ++i) Csum[i] = ((float)h[i] + (float)h[n + i]) + (float)h[2 * n + i];
-  }
-  return 0;
-}
-
-// the split2h k-major x k-major weight grad alone (mtsac_debug.h)
-int mtsac_debug_gemm_x3p_kmajor(int E, int M, int N, int K, int slices, const float* A, const float* B, float* C) {
-  if (E < 1 || E > 8 || M < 1 || N < 1 || K < 1 || slices < 1 || slices > 64 || slices > (int)(up32(K) / 32) || !A ||
-      !B || !C || (long long)E * K * std::max(M, N) >= (1LL << 28))
-    return -22;
-  if (hipSetDevice(0) != hipSuccess) return -5;
-  const int Kp = (int)up32(K);
-  long long lda, pa, ldb, pb;
-  plane_geom(M, K, true, lda, pa);
-  plane_geom(N, K, true, ldb, pb);
-  // the operands' records as a producer leaves them: max |x| and the plane exponent of that bound
-  PlaneRec hrec[2];
-  std::memset(hrec, 0, sizeof hrec);
-  const float ma = host_amax(A, (size_t)E * K * M), mb = host_amax(B, (size_t)E * K * N);
-  hrec[0].e = host_plane_exp(ma); hrec[0].amax[0] = ma;
-  hrec[1].e = host_plane_exp(mb); hrec[1].amax[0] = mb;
-  Guarded gd;
-  const PlaneRec* rec = gd.in(hrec, 2);
-  const float *dA = gd.in(A, (size_t)E * K * M), *dB = gd.in(B, (size_t)E * K * N);
-  __bf16* Ap = gd.mem.get<__bf16>((size_t)3 * pa * E);
-  __bf16* Bp = gd.mem.get<__bf16>((size_t)3 * pb * E);
-  float* dC = gd.out<float>((size_t)E * M * N, "C");  // starts as NaN between two guard bands
-  float* ws = gd.mem.get<float>((size_t)std::max(gemm_ws_floats(M, N, E, std::max(slices, 2)), 1LL));
-  if (!gd.ok || !Ap || !Bp || !ws) return -12;
-  for (int z = 0; z < E; ++z) {
-    split_into(dA + (size_t)z * K * M, M, K, true, Ap + 3 * pa * z, &rec[0].e);
-    split_into(dB + (size_t)z * K * N, N, K, true, Bp + 3 * pb * z, &rec[1].e);
-  }
-  SplitGemmParams g{};
-  g.np = 2;
-  g.ra = rec; g.na = 1; g.rb = rec + 1; g.nb = 1;
-  g.kmul = (float)K;
-  g.A = Ap; g.lda = lda; g.pA = pa; g.sA = 3 * pa; g.a_kmajor = 1;
-  g.B = Bp; g.ldb = ldb; g.pB = pb; g.sB = 3 * pb; g.b_kmajor = 1;
-  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
-  g.M = M; g.N = N; g.K = Kp;
-  g.splits = slices;
-  g.ws = ws;
-  gemm_x3p(g, EPI_STORE, E, nullptr);
-  int rc = 0;
-  if ((rc = sync_rc("gemm_x3p k-major")) || (rc = gd.check())) return rc;
-  return gd.back(C, dC, (size_t)E * M * N) ? 0 : -5;
-}
-
-int mtsac_debug_gemm_x3p_bench(int epi, int batch, int M, int N, int K, int iters, double* ms_per_launch) {
-  const int layout = (epi >> 8) & 3;  // bit 0: A k-major, bit 1: B k-major
-  const int splits = (epi >> 16) & 255;  // split-K slices (0/1: none; EPI_STORE: + splitk_reduce; 255: auto)
-  const bool fin = (epi >> 12) & 1;      // arrival counters: the weight grads' in-launch reduce
-  const bool h2 = (epi >> 13) & 1;       // precision split2h (zero exponents: operands in [-1, 1])
-  const bool pout = (epi >> 14) & 1;     // output planes too (the forward's: bias+ReLU planes out)
-  epi &= 255;
-  if (M < 1 || N < 1 || K < 1 || batch < 1 || iters < 1 || !ms_per_launch) return -22;
-  DevBuf d;
-  PlaneRec* rec = h2 ? d.get<PlaneRec>(3) : nullptr;
-  float* fa = d.get<float>((size_t)M * K);
-  float* fb = d.get<float>((size_t)N * K);
-  float* C = d.get<float>((size_t)M * N * batch);
-  float* bias = d.get<float>((size_t)N * batch);
-  if (!fa || !fb || !C || !bias) return -12;
-  hipLaunchKernelGGL(fill_rand_f32, dim3((unsigned)(((long long)M * K + 255) / 256)), dim3(256), 0, nullptr, fa,
-                     (long long)M * K, 3u);
-  hipLaunchKernelGGL(fill_rand_f32, dim3((unsigned)(((long long)N * K + 255) / 256)), dim3(256), 0, nullptr, fb,
-                     (long long)N * K, 5u);
-  // one plane set per batch entry (distinct memory, same values)
-  long long lda, pa, ldb, pb;
-  plane_geom(M, K, layout & 1, lda, pa);
-  plane_geom(N, K, layout & 2, ldb, pb);
-  __bf16* Ap = d.get<__bf16>((size_t)3 * pa * batch);
-  __bf16* Bp = d.get<__bf16>((size_t)3 * pb * batch);
-  if (!Ap || !Bp) return -12;
-  for (int z = 0; z < batch; ++z) {
-    split_into(fa, M, K, layout & 1, Ap + 3 * pa * z, h2 ? &rec[0].e : nullptr);
-    split_into(fb, N, K, layout & 2, Bp + 3 * pb * z, h2 ? &rec[1].e : nullptr);
-  }
-  SplitGemmParams g{};
-  if (h2) {
-    g.np = 2;
-    g.ra = rec; g.rb = rec + 1; g.rc = rec + 2;
-    g.kmul = (float)K;
-  }
-  if (pout) {
-    __bf16* Cp = d.get<__bf16>((size_t)3 * M * N * batch);
-    if (!Cp) return -12;
-    g.Cp = Cp; g.ldcp = N; g.pC = (long long)M * N; g.sCp = 3 * g.pC;
-  }
-  const bool planes_only = pout;
-  g.A = Ap; g.lda = lda; g.pA = pa; g.sA = 3 * pa; g.a_kmajor = layout & 1;
-  g.B = Bp; g.ldb = ldb; g.pB = pb; g.sB = 3 * pb; g.b_kmajor = (layout >> 1) & 1;
-  g.C = planes_only ? nullptr : C; g.ldc = N; g.sC = (long long)M * N;
-  g.bias = bias; g.sBias = N;
-  g.mask = C; g.ldm = N; g.sMask = (long long)M * N;
-  g.M = M; g.N = N; g.K = (int)up32(K);
-  if (splits > 1) {
-    g.splits = splits == 255 ? -1 : splits;
-    const int sw = splits == 255 ? gemm_x3p_splits(M, N, g.K, batch, layout == 3) : splits;
-    g.ws = d.get<float>((size_t)M * N * batch * std::max(sw, 1));
-    if (!g.ws) return -12;
-    if (fin) {
-      g.cnt = d.get<int>((size_t)GEMM_X3F_CNT);
-      if (!g.cnt) return -12;
-    }
-  }
-  gemm_x3p(g, epi, batch, nullptr);
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -5;
-  (void)hipEventRecord(e0, nullptr);
-  for (int i = 0; i < iters; ++i) gemm_x3p(g, epi, batch, nullptr);
-  (void)hipEventRecord(e1, nullptr);
-  if (hipEventSynchronize(e1) != hipSuccess) return -5;
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  *ms_per_launch = ms / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return 0;
-}
-
-// gemm_x3f (row-major x row-major planes, K % 64 == 0): C[M][N] = A[M][K] . B[N][K]^T from host
-// fp32 arrays, epi 1 bias+ReLU / 2 ReLU mask (fp32 mask, or with bit 8 of epi its bf16 high
-// plane); Csum (nullable) receives the sum of the written planes.  -95 when gemm_x3f does not take
-// the shape (too few tiles, layout).
-int mtsac_debug_gemm_x3f(int epi, int batch, int M, int N, int K, const float* A, const float* B, float* C,
-                         const float* bias, const float* mask, float* Csum) {
-  const bool m16 = (epi >> 8) & 1;
-  const bool small = (epi >> 9) & 1;  // gemm_x3s instead
-  const int np = ((epi >> 10) & 1) ? 1 : 3;  // bf16: the high plane only
-  const bool autosplit = (epi >> 11) & 1;     // split-K by the launcher's own choice (workspace given)
-  const bool fin = (epi >> 12) & 1;           // ... with arrival counters: the in-launch finish
-  const bool h2 = (epi >> 13) & 1;            // precision split2h: fp16 planes scaled per tensor
-  const bool bfrag = (epi >> 14) & 1;         // B planes in the fragment layout (N % 16 == 0)
-  epi &= 255;
-  if (M < 1 || N < 1 || K < 1 || batch < 1 || !A || !B || !C) return -22;
-  if (bfrag && N % 16 != 0) return -22;
-  DevBuf d;
-  const size_t nA = (size_t)M * K * batch, nB = (size_t)N * K * batch, nC = (size_t)M * N * batch;
-  // split2h: records of A, B (its max covering the bias, as a trunk record does), the mask and C
-  PlaneRec* rec = d.get<PlaneRec>(4);
-  if (!rec) return -12;
-  if (h2) {
-    auto amax = [](const float* x, size_t n) {
-      float m = 0.f;
-      for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(x[i]));
-      return m;
-    };
-    auto pexp = [](float b) {
-      b *= 1.00390625f;
-      if (!(b > 0.f)) return 0;
-      int ex;
-      (void)std::frexp(b, &ex);
-      return 15 - ex;
-    };
-    const float ma = amax(A, nA), mbias = (epi == 1 && bias) ? amax(bias, (size_t)N * batch) : 0.f;
-    const float mb = std::max(amax(B, nB), mbias);
-    const float mm = mask ? amax(mask, nC) : 1.f;
-    std::vector<PlaneRec> h(4);
-    std::memset(h.data(), 0, sizeof(PlaneRec) * 4);
-    h[0].e = pexp(ma); h[0].amax[0] = ma;
-    h[1].e = pexp(mb); h[1].amax[0] = mb;
-    h[2].e = pexp(mm); h[2].amax[0] = mm;
-    (void)hipMemcpy(rec, h.data(), sizeof(PlaneRec) * 4, hipMemcpyHostToDevice);
-  }
-  float* dA = d.get<float>(nA);
-  float* dB = d.get<float>(nB);
-  float* dC = d.get<float>(nC);
-  float* dbias = d.get<float>((size_t)N * batch);
-  float* dmask = d.get<float>(nC);
-  __bf16* dCp = d.get<__bf16>(3 * nC);
-  __bf16* dM16 = d.get<__bf16>(3 * nC);
-  if (!dA || !dB || !dC || !dbias || !dmask || !dCp || !dM16) return -12;
-  (void)hipMemcpy(dA, A, sizeof(float) * nA, hipMemcpyHostToDevice);
-  (void)hipMemcpy(dB, B, sizeof(float) * nB, hipMemcpyHostToDevice);
-  if (bias) (void)hipMemcpy(dbias, bias, sizeof(float) * N * batch, hipMemcpyHostToDevice);
-  if (mask) (void)hipMemcpy(dmask, mask, sizeof(float) * nC, hipMemcpyHostToDevice);
-  const long long Kp = (K + 63) / 64 * 64;
-  __bf16* Ap = d.get<__bf16>((size_t)3 * M * Kp * batch);
-  __bf16* Bp = d.get<__bf16>((size_t)3 * N * Kp * batch);
-  if (!Ap || !Bp) return -12;
-  for (int z = 0; z < batch; ++z) {
-    SplitParams s{};
-    s.x = dA + (size_t)z * M * K; s.ldx = K; s.rows = M; s.cols = K;
-    s.out = Ap + (size_t)z * 3 * M * Kp; s.ldo = Kp; s.po = (long long)M * Kp; s.out_rows = M; s.out_cols = (int)Kp;
-    s.e2h = h2 ? &rec[0].e : nullptr;
-    split_planes(s, false, 1, nullptr);
-    s.x = dB + (size_t)z * N * K; s.rows = N;
-    s.out = Bp + (size_t)z * 3 * N * Kp; s.po = (long long)N * Kp; s.out_rows = N;
-    s.e2h = h2 ? &rec[1].e : nullptr;
-    s.frag = bfrag ? 1 : 0;
-    split_planes(s, false, 1, nullptr);
-    s.frag = 0;
-    if (m16) {  // planes of the mask, row stride N
-      s.x = dmask + (size_t)z * M * N; s.ldx = N; s.rows = M; s.cols = N;
-      s.out = dM16 + (size_t)z * 3 * M * N; s.ldo = N; s.po = (long long)M * N; s.out_rows = M; s.out_cols = N;
-      s.e2h = h2 ? &rec[2].e : nullptr;
-      split_planes(s, false, 1, nullptr);
-    }
-  }
-  SplitGemmParams g{};
-  g.A = Ap; g.lda = Kp; g.pA = (long long)M * Kp; g.sA = 3 * g.pA;
-  g.B = Bp; g.ldb = Kp; g.pB = (long long)N * Kp; g.sB = 3 * g.pB;
-  g.b_frag = bfrag ? 1 : 0;
-  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
-  g.bias = dbias; g.sBias = N;
-  g.mask = dmask; g.ldm = N; g.sMask = (long long)M * N;
-  if (m16) {
-    g.mask16 = dM16;
-    g.sMask = 3ll * M * N;
-  }
-  if (Csum) {
-    g.Cp = dCp; g.ldcp = N; g.pC = (long long)M * N; g.sCp = 3 * g.pC;
-  }
-  g.M = M; g.N = N; g.K = (int)Kp;
-  g.np = h2 ? 2 : np;
-  if (h2) {
-    g.ra = rec + 0; g.na = 1;
-    g.rb = rec + 1; g.nb = 1;
-    g.rc = rec + 3;
-    g.bias_in_b = epi == 1 && bias ? 1 : 0;
-    g.pMask = (long long)M * N;
-    g.kmul = (float)K;
-  }
-  if (autosplit) {
-    g.ws = d.get<float>((size_t)std::max(gemm_x3f_ws_floats(M, N, (int)Kp, batch), 1LL));
-    if (!g.ws) return -12;
-    g.splits = -1;
-    if (fin) {
-      g.cnt = d.get<int>((size_t)GEMM_X3F_CNT);
-      if (!g.cnt || hipMemset(g.cnt, 0, sizeof(int) * GEMM_X3F_CNT) != hipSuccess) return -12;
-    }
-  }
-  if (small) {
-    if (!gemm_x3s_ok(g, epi, batch)) return -95;
-    gemm_x3s(g, epi, batch, nullptr);
-  } else {
-    if (!gemm_x3f_ok(g, epi, batch)) return -95;
-    gemm_x3f(g, epi, batch, nullptr);
-  }
-  {
-    const hipError_t le = hipGetLastError();  // a launch the runtime refused leaves C as it was
-    if (le != hipSuccess) {
-      fprintf(stderr, "[mtsac_debug_gemm_x3f] launch refused: %s\n", hipGetErrorString(le));
-      return -6;
-    }
-  }
-  if (hipDeviceSynchronize() != hipSuccess) return -5;
-  if (hipMemcpy(C, dC, sizeof(float) * nC, hipMemcpyDeviceToHost) != hipSuccess) return -5;
-  if (Csum && h2) {  // (h + l) 2^-ec
-    std::vector<_Float16> h(3 * nC);
-    int ec = 0;
-    if (hipMemcpy(h.data(), dCp, sizeof(_Float16) * h.size(), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&ec, &rec[3].e, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-      return -5;
-    const size_t n = (size_t)M * N;
-    for (int z = 0; z < batch; ++z)
-      for (size_t i = 0; i < n; ++i) {
-        const _Float16* q = &h[(size_t)z * 3 * n];
-        Csum[(size_t)z * n + i] = std::ldexp((float)q[i] + (float)q[n + i], -ec);
-      }
-  } else if (Csum) {
-    std::vector<__bf16> h(3 * nC);
-    if (hipMemcpy(h.data(), dCp, sizeof(__bf16) * h.size(), hipMemcpyDeviceToHost) != hipSuccess) return -5;
-    const size_t n = (size_t)M * N;
-    for (int z = 0; z < batch; ++z)
-      for (size_t i = 0; i < n; ++i) {
-        const __bf16* q = &h[(size_t)z * 3 * n];
-        Csum[(size_t)z * n + i] = ((float)q[i] + (float)q[n + i]) + (float)q[2 * n + i];
-      }
-  }
-  return 0;
-}
-
-// The ragged split2h data grad (gemm_x3f_ragged) beside the dense launch it replaces, on host arrays, E = 2:
-// A [2][B][K] (dz), W [2][N][K], mask [2][B][N] (the activation), active [2][B] bytes.  The dense launch runs
-// on A with the inactive rows zeroed; the ragged one on A's active rows compacted in ascending row order
-// (lists from active_rows on dq = active ? -1 : 0), both at the same plane exponents, whatever the tile
-// count (the engine's >= 192-workgroup policy is not asked).  flags bit 0: planes out (else fp32), bit 1:
-// W planes in the fragment layout (N % 16 == 0).  dense_out / rag_out: fp32 [2][B][N], or the two fp16
-// planes as 16-bit words [2][2][B][N]; the ragged buffer and its record's partial maxima start as 0xFF
-// bytes / 1e30.  rows_out [2][B]: the lists (0xFF words past n_e).  info [6]: the dense and ragged output
-// exponents, the max over the partial maxima of each (float bits), n_0, n_1.
-int mtsac_debug_gemm_x3f_ragged(int flags, int B, int N, int K, const float* A, const float* W, const float* mask,
-                                const unsigned char* active, void* dense_out, void* rag_out, int* rows_out,
-                                int* info) {
-  const bool pout = flags & 1, bfrag = (flags >> 1) & 1;
-  if (B < 1 || N < 8 || N % 8 != 0 || K < 1 || !A || !W || !mask || !active || !dense_out || !rag_out || !rows_out ||
-      !info || (bfrag && N % 16 != 0))
-    return -22;
-  const int E = 2;
-  const size_t nA = (size_t)E * B * K, nW = (size_t)E * N * K, nC = (size_t)E * B * N;
-  // host: dq, A with the inactive rows zeroed
-  std::vector<float> dq((size_t)E * B), Az(A, A + nA);
-  for (int e = 0; e < E; ++e)
-    for (int b = 0; b < B; ++b) {
-      const bool on = active[(size_t)e * B + b] != 0;
-      dq[(size_t)e * B + b] = on ? -1.f : 0.f;
-      if (!on) std::fill(Az.begin() + ((size_t)e * B + b) * K, Az.begin() + ((size_t)e * B + b + 1) * K, 0.f);
-    }
-  Guarded gd;
-  float* d_dq = gd.in(dq.data(), dq.size());
-  float* dAz = gd.in(Az.data(), nA);
-  float* dW = gd.in(W, nW);
-  float* dmask = gd.in(mask, nC);
-  int* d_n = gd.out<int>(E, "n");
-  int* d_rows = gd.out<int>((size_t)E * B, "rows");
-  int* d_slot = gd.out<int>((size_t)E * B, "slot");
-  if (!gd.ok) return -12;
-  active_rows(d_dq, E, B, d_n, d_rows, d_slot, nullptr);
-  if (int rc = sync_rc("active_rows")) return rc;
-  std::vector<int> hn(E), hrows((size_t)E * B);
-  if (!gd.back(hn.data(), d_n, E) || !gd.back(hrows.data(), d_rows, hrows.size())) return -5;
-  for (int e = 0; e < E; ++e)
-    if (hn[e] < 0 || hn[e] > B) return -5;
-  std::vector<float> Ac(nA, 0.f);  // compacted (rows past n_e: zeros, never read)
-  for (int e = 0; e < E; ++e)
-    for (int s2 = 0; s2 < hn[e]; ++s2) {
-      const int b = hrows[(size_t)e * B + s2];
-      if (b < 0 || b >= B) return -5;
-      std::copy(Az.begin() + ((size_t)e * B + b) * K, Az.begin() + ((size_t)e * B + b + 1) * K,
-                Ac.begin() + ((size_t)e * B + s2) * K);
-    }
-  float* dAc = gd.in(Ac.data(), nA);
-  // records: A, W, mask, dense out, ragged out
-  auto amax = [](const float* x, size_t n) {
-    float m = 0.f;
-    for (size_t i = 0; i < n; ++i) m = std::max(m, std::fabs(x[i]));
-    return m;
-  };
-  auto pexp = [](float b) {
-    b *= 1.00390625f;
-    if (!(b > 0.f)) return 0;
-    int ex;
-    (void)std::frexp(b, &ex);
-    return 15 - ex;
-  };
-  std::vector<PlaneRec> hrec(5);
-  std::memset(hrec.data(), 0, sizeof(PlaneRec) * hrec.size());
-  const float ma = amax(Az.data(), nA), mw = amax(W, nW), mm = amax(mask, nC);
-  hrec[0].e = pexp(ma); hrec[0].amax[0] = ma;
-  hrec[1].e = pexp(mw); hrec[1].amax[0] = mw;
-  hrec[2].e = pexp(mm); hrec[2].amax[0] = mm;
-  hrec[3].e = hrec[4].e = 0x7fffffff;
-  for (int i = 0; i < PLANE_REC_PARTS; ++i) hrec[3].amax[i] = hrec[4].amax[i] = 1e30f;  // poison: a stale slot shows
-  PlaneRec* rec = gd.in(hrec.data(), hrec.size());
-  const long long Kp = (K + 63) / 64 * 64;
-  __bf16* Azp = gd.mem.get<__bf16>((size_t)3 * B * Kp * E);
-  __bf16* Acp = gd.mem.get<__bf16>((size_t)3 * B * Kp * E);
-  __bf16* Wp = gd.mem.get<__bf16>((size_t)3 * N * Kp * E);
-  __bf16* Mp = gd.mem.get<__bf16>(3 * nC);
-  const size_t out_bytes = pout ? nC * 2 * sizeof(__bf16) : nC * sizeof(float);
-  unsigned char* dden = gd.out<unsigned char>(out_bytes, "dense out");
-  unsigned char* drag = gd.out<unsigned char>(out_bytes, "ragged out");
-  if (!gd.ok || !dAc || !rec || !Azp || !Acp || !Wp || !Mp) return -12;
-  for (int z = 0; z < E; ++z) {
-    SplitParams sp{};
-    sp.ldx = K; sp.rows = B; sp.cols = K; sp.ldo = Kp; sp.po = (long long)B * Kp; sp.out_rows = B; sp.out_cols = (int)Kp;
-    sp.e2h = &rec[0].e;
-    sp.x = dAz + (size_t)z * B * K; sp.out = Azp + (size_t)z * 3 * B * Kp;
-    split_planes(sp, false, 1, nullptr);
-    sp.x = dAc + (size_t)z * B * K; sp.out = Acp + (size_t)z * 3 * B * Kp;
-    split_planes(sp, false, 1, nullptr);
-    sp.x = dW + (size_t)z * N * K; sp.rows = N; sp.out = Wp + (size_t)z * 3 * N * Kp; sp.po = (long long)N * Kp;
-    sp.out_rows = N; sp.e2h = &rec[1].e; sp.frag = bfrag ? 1 : 0;
-    split_planes(sp, false, 1, nullptr);
-    sp.frag = 0;
-    sp.x = dmask + (size_t)z * B * N; sp.ldx = N; sp.rows = B; sp.cols = N;
-    sp.out = Mp + (size_t)z * 3 * B * N; sp.ldo = N; sp.po = (long long)B * N; sp.out_rows = B; sp.out_cols = N;
-    sp.e2h = &rec[2].e;
-    split_planes(sp, false, 1, nullptr);
-  }
-  SplitGemmParams g{};
-  g.np = 2;
-  g.lda = Kp; g.pA = (long long)B * Kp; g.sA = 3 * g.pA;
-  g.B = Wp; g.ldb = Kp; g.pB = (long long)N * Kp; g.sB = 3 * g.pB;
-  g.b_frag = bfrag ? 1 : 0;
-  g.mask16 = Mp; g.ldm = N; g.sMask = 3ll * B * N; g.pMask = (long long)B * N;
-  g.M = B; g.N = N; g.K = (int)Kp;
-  g.ra = rec + 0; g.na = 1;
-  g.rb = rec + 1; g.nb = 1;
-  g.kmul = (float)K;
-  int nparts[2] = {0, 0};
-  auto outs = [&](unsigned char* o, PlaneRec* rc, int* np_) {
-    g.C = nullptr; g.Cp = nullptr; g.rc = nullptr;
-    if (pout) {
-      g.Cp = reinterpret_cast<__bf16*>(o); g.ldcp = N; g.pC = (long long)B * N; g.sCp = 2 * g.pC;
-      g.rc = rc;
-    } else {
-      g.C = reinterpret_cast<float*>(o); g.ldc = N; g.sC = (long long)B * N;
-    }
-    g.nparts = np_;
-  };
-  g.A = Azp;
-  outs(dden, rec + 3, &nparts[0]);
-  gemm_x3f(g, EPI_RELU_MASK, E, nullptr);  // no workspace: the plain unsplit launch
-  if (int rc = sync_rc("dense gemm_x3f")) return rc;
-  g.A = Acp;
-  outs(drag, rec + 4, &nparts[1]);
-  g.rag_n = d_n; g.rag_rows = d_rows; g.rag_ld = B;
-  gemm_x3f_ragged(g, nullptr);
-  if (int rc = sync_rc("gemm_x3f_ragged")) return rc;
-  if (int rc = gd.check()) return rc;
-  if (!gd.back(reinterpret_cast<unsigned char*>(dense_out), dden, out_bytes) ||
-      !gd.back(reinterpret_cast<unsigned char*>(rag_out), drag, out_bytes) ||
-      !gd.back(hrec.data(), rec, hrec.size()))
-    return -5;
-  std::copy(hrows.begin(), hrows.end(), rows_out);
-  for (int k = 0; k < 2; ++k) {
-    float m = 0.f;
-    for (int i = 0; i < nparts[k] && i < PLANE_REC_PARTS; ++i) m = std::max(m, hrec[3 + k].amax[i]);
-    info[k] = hrec[3 + k].e;
-    std::memcpy(&info[2 + k], &m, sizeof(float));
-  }
-  info[4] = hn[0];
-  info[5] = hn[1];
-  return 0;
-}
-
-// time iters launches of the forward-shaped plane GEMM (C = relu(A . B^T + bias) with planes out)
-// on device-resident random planes; which: 0 = gemm_x3p (row-major A, k-major B: the engine's
-// current forward), 1 = gemm_x3f (row-major both)
-int mtsac_debug_gemm_fwd_bench(int which, int epi, int batch, int M, int N, int K, int iters, double* ms_per_launch) {
-  const int outs = (epi >> 8) & 3;  // 0: fp32 + planes, 1: planes only, 2: fp32 only
-  const int np = ((epi >> 10) & 1) ? 1 : 3;  // bf16: the high plane only
-  const bool autosplit = (epi >> 11) & 1;     // split-K by the launcher's own choice (workspace given)
-  const bool fin = (epi >> 12) & 1;           // ... with arrival counters: the in-launch finish
-  const bool h2 = (epi >> 13) & 1;            // precision split2h (exponents 0: operands in [-1, 1])
-  const bool bfrag = (epi >> 14) & 1;         // gemm_x3f: B planes in the fragment layout
-  epi &= 255;
-  if (M < 1 || N < 1 || K < 1 || batch < 1 || iters < 1 || !ms_per_launch) return -22;
-  DevBuf d;
-  const long long Kp = (K + 63) / 64 * 64;
-  PlaneRec* rec = d.get<PlaneRec>(3);  // zero exponents: the random operands lie in [-1, 1]
-  if (!rec) return -12;
-  float* fa = d.get<float>((size_t)M * Kp);
-  float* fb = d.get<float>((size_t)N * Kp);
-  float* C = d.get<float>((size_t)M * N * batch);
-  float* bias = d.get<float>((size_t)N * batch);
-  __bf16* Cp = d.get<__bf16>((size_t)3 * M * N * batch);
-  if (!fa || !fb || !C || !bias || !Cp) return -12;
-  hipLaunchKernelGGL(fill_rand_f32, dim3((unsigned)(((long long)M * Kp + 255) / 256)), dim3(256), 0, nullptr, fa,
-                     (long long)M * Kp, 3u);
-  hipLaunchKernelGGL(fill_rand_f32, dim3((unsigned)(((long long)N * Kp + 255) / 256)), dim3(256), 0, nullptr, fb,
-                     (long long)N * Kp, 5u);
-  const bool bk = which == 0;  // gemm_x3p forward: B k-major [K][N]
-  long long lda, pa, ldb, pb;
-  plane_geom(M, (int)Kp, false, lda, pa);
-  plane_geom(N, (int)Kp, bk, ldb, pb);
-  __bf16* Ap = d.get<__bf16>((size_t)3 * pa * batch);
-  __bf16* Bp = d.get<__bf16>((size_t)3 * pb * batch);
-  if (!Ap || !Bp) return -12;
-  for (int z = 0; z < batch; ++z) {
-    split_into(fa, M, (int)Kp, false, Ap + 3 * pa * z, h2 ? &rec[0].e : nullptr);
-    split_into(fb, N, (int)Kp, bk, Bp + 3 * pb * z, h2 ? &rec[1].e : nullptr, bfrag && !bk);
-  }
-  SplitGemmParams g{};
-  if (h2) {
-    g.ra = rec; g.rb = rec + 1; g.rc = rec + 2;
-    g.kmul = (float)K;
-    g.pMask = (long long)M * N;
-  }
-  g.A = Ap; g.lda = lda; g.pA = pa; g.sA = 3 * pa;
-  g.B = Bp; g.ldb = ldb; g.pB = pb; g.sB = 3 * pb; g.b_kmajor = bk;
-  g.b_frag = bfrag && !bk ? 1 : 0;
-  g.C = C; g.ldc = N; g.sC = (long long)M * N;
-  g.bias = bias; g.sBias = N;
-  g.mask = C; g.ldm = N; g.sMask = (long long)M * N;
-  g.Cp = Cp; g.ldcp = N; g.pC = (long long)M * N; g.sCp = 3 * g.pC;
-  if (outs == 1) g.C = nullptr;
-  if (outs == 2) g.Cp = nullptr;
-  g.M = M; g.N = N; g.K = (int)Kp;
-  g.splits = 1;
-  g.np = h2 ? 2 : np;
-  if (autosplit) {
-    const long long wsf = std::max(gemm_x3f_ws_floats(M, N, (int)Kp, batch), gemm_x3p_ws_floats(M, N, (int)Kp, batch, false));
-    g.ws = d.get<float>((size_t)std::max(wsf, 1LL));
-    if (!g.ws) return -12;
-    g.splits = -1;
-    if (fin) {
-      g.cnt = d.get<int>((size_t)GEMM_X3F_CNT);
-      if (!g.cnt) return -12;
-    }
-  }
-  if (which >= 1 && !gemm_x3f_ok(g, epi, batch)) return -95;
-  if (which < 0 && !gemm_x3s_ok(g, epi, batch)) return -95;
-  auto run = [&]() {
-    if (which == -1) gemm_x3s(g, epi, batch, nullptr);
-    else if (which < -1) gemm_x3s_ablate(g, -1 - which, batch, nullptr);  // -2 no loads, -3 no MFMAs
-    else if (which >= 2) gemm_x3f_ablate(g, which - 2, batch, nullptr);  // 2 + ablation bits (planes out)
-    else if (which == 1) gemm_x3f(g, epi, batch, nullptr);
-    else gemm_x3p(g, epi, batch, nullptr);
-  };
-  run();
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -5;
-  (void)hipEventRecord(e0, nullptr);
-  for (int i = 0; i < iters; ++i) run();
-  (void)hipEventRecord(e1, nullptr);
-  if (hipEventSynchronize(e1) != hipSuccess) return -5;
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  *ms_per_launch = ms / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return 0;
-}
-
-int mtsac_debug_x3p_geo(int geo) {
-  const int old = g_x3p_geo;
-  if (geo < 0) {  // restore the default (e.g. the value this function returned)
-    g_x3p_geo = -1;
-    g_x3p_dbg = g_x3_dbg = 0;
-    return old;
-  }
-  const int g = geo & 255;
-  g_x3p_geo = g <= 5 ? g : -1;
-  g_x3p_dbg = (geo >> 8) & 255;
-  g_x3_dbg = (geo >> 16) & 255;
-  return old;
-}
-
-int mtsac_debug_x3s_ti(int M, int N, int batch) { return gemm_x3s_ti(M, N, batch); }
 
 // DrQ conv channel groups per lane (0 = the engine's choice); returns the previous fwd | bwd << 8
 int mtsac_debug_drq_groups(int fwd, int bwd) {
@@ -1341,217 +589,6 @@ int mtsac_debug_head_row_alpha(int B, int T_l, int T_glob, int task_begin, int u
   int rc = 0;
   if ((rc = sync_rc("row_alpha")) || (rc = g.check())) return rc;
   return g.back(alpha_row, d_a, (size_t)B) && g.back(tw_row, d_tw, (size_t)B) ? 0 : -5;
-}
-
-// gemm_x3f / gemm_x3s as the engine's trunk calls them (mtsac_debug.h): padded plane strides, guarded
-// outputs, the bias grad's column-sum partials and their finish over the engine's own chunk count
-int mtsac_debug_gemm_x3f_ld(int epi, int batch, int M, int N, int K, int ld_n, int rows_p, const float* A,
-                            const float* B, float* C, const float* bias, const float* mask, float* Csum, float* dbp,
-                            float* db, int* info) {
-  const bool m16 = (epi >> 8) & 1;
-  const bool small = (epi >> 9) & 1;          // gemm_x3s instead
-  const int np = ((epi >> 10) & 1) ? 1 : 3;   // bf16: the high plane only
-  const bool autosplit = (epi >> 11) & 1;     // split-K by the launcher's own choice (workspace given)
-  const bool fin = (epi >> 12) & 1;           // ... with arrival counters: the in-launch finish
-  const bool h2 = (epi >> 13) & 1;            // precision split2h
-  const bool bfrag = (epi >> 14) & 1;         // B planes in the fragment layout (N % 16 == 0)
-  const bool ponly = (epi >> 15) & 1;         // planes only: the engine's data-grad form
-  epi &= 255;
-  if (M < 1 || N < 1 || K < 1 || batch < 1 || batch > 8 || ld_n < N || ld_n % 4 != 0 || rows_p < M || !A || !B ||
-      !Csum || !dbp || !db || !info || (!ponly && !C) || (epi != EPI_BIAS_RELU && epi != EPI_RELU_MASK) ||
-      (epi == EPI_BIAS_RELU && !bias) || (epi == EPI_RELU_MASK && !mask) || (bfrag && N % 16 != 0) ||
-      (h2 && np == 1) || (long long)batch * rows_p * ld_n >= (1LL << 28))
-    return -22;
-  if (hipSetDevice(0) != hipSuccess) return -5;
-  const long long Kp = small ? up32(K) : (K + 63) / 64 * 64;  // gemm_x3s steps K by 32 (the engine's padded width)
-  const size_t nA = (size_t)M * K * batch, nB = (size_t)N * K * batch, nC = (size_t)M * N * batch;
-  const long long pp = (long long)rows_p * ld_n;  // plane stride of the output and mask planes
-  const int maxrt = gemm_x3f_max_row_tiles(M);
-  Guarded gd;
-  std::vector<PlaneRec> hrec(4);
-  std::memset(hrec.data(), 0, sizeof(PlaneRec) * 4);
-  if (h2) {  // records of A, B (its max covering the bias, as a trunk record does), the mask and C
-    const float ma = host_amax(A, nA), mbias = epi == EPI_BIAS_RELU ? host_amax(bias, (size_t)N * batch) : 0.f;
-    const float mb = std::max(host_amax(B, nB), mbias), mm = mask ? host_amax(mask, nC) : 1.f;
-    hrec[0].e = host_plane_exp(ma); hrec[0].amax[0] = ma;
-    hrec[1].e = host_plane_exp(mb); hrec[1].amax[0] = mb;
-    hrec[2].e = host_plane_exp(mm); hrec[2].amax[0] = mm;
-  }
-  PlaneRec* rec = gd.in(hrec.data(), 4);
-  const float *dA = gd.in(A, nA), *dB = gd.in(B, nB), *dbias = gd.in(bias, (size_t)N * batch), *dmask = gd.in(mask, nC);
-  __bf16* Ap = gd.mem.get<__bf16>((size_t)3 * rows_p * Kp * batch);
-  __bf16* Bp = gd.mem.get<__bf16>((size_t)3 * N * Kp * batch);
-  __bf16* Mp = m16 ? gd.mem.get<__bf16>((size_t)3 * pp * batch) : nullptr;
-  float* dC = ponly ? nullptr : gd.out<float>(nC, "C");
-  __bf16* dCp = gd.out<__bf16>((size_t)3 * pp * batch, "C planes");
-  float* d_dbp = gd.out<float>((size_t)batch * maxrt * N, "dbp");
-  float* d_db = gd.out<float>((size_t)batch * N, "db");
-  if (!gd.ok || !rec || !Ap || !Bp || (m16 && !Mp)) return -12;
-  SplitGemmParams g{};
-  g.A = Ap; g.lda = Kp; g.pA = (long long)rows_p * Kp; g.sA = 3 * g.pA;
-  g.B = Bp; g.ldb = Kp; g.pB = (long long)N * Kp; g.sB = 3 * g.pB;
-  g.b_frag = bfrag ? 1 : 0;
-  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
-  g.bias = dbias; g.sBias = N;
-  if (m16) {
-    g.mask16 = Mp; g.ldm = ld_n; g.sMask = 3 * pp;
-  } else {
-    g.mask = dmask; g.ldm = N; g.sMask = (long long)M * N;
-  }
-  g.pMask = pp;
-  g.Cp = dCp; g.ldcp = ld_n; g.pC = pp; g.sCp = 3 * pp;
-  g.M = M; g.N = N; g.K = (int)Kp;
-  g.np = h2 ? 2 : np;
-  g.dbp = d_dbp;
-  int nparts = 0;
-  g.nparts = &nparts;
-  if (h2) {
-    g.ra = rec + 0; g.na = 1;
-    g.rb = rec + 1; g.nb = 1;
-    g.rc = rec + 3;
-    g.bias_in_b = epi == EPI_BIAS_RELU ? 1 : 0;
-    g.kmul = (float)K;
-  }
-  if (autosplit) {
-    g.ws = gd.mem.get<float>((size_t)std::max(gemm_x3f_ws_floats(M, N, (int)Kp, batch), 1LL));
-    if (!g.ws) return -12;
-    g.splits = -1;
-    if (fin && !(g.cnt = gd.mem.get<int>((size_t)GEMM_X3F_CNT))) return -12;  // zeroed
-  }
-  if (small ? !gemm_x3s_ok(g, epi, batch) : !gemm_x3f_ok(g, epi, batch)) return -95;
-  // rows per column-sum chunk and the chunk count, by the rule the engine's dgrad_params uses
-  const int bm = dbp_chunk_rows(g, epi, batch, !small);
-  const int chunks = (M + bm - 1) / bm;
-  if (chunks > maxrt) return -95;
-  for (int z = 0; z < batch; ++z) {
-    SplitParams s{};
-    s.x = dA + (size_t)z * M * K; s.ldx = K; s.rows = M; s.cols = K;
-    s.out = Ap + (size_t)z * 3 * rows_p * Kp; s.ldo = Kp; s.po = (long long)rows_p * Kp; s.out_rows = rows_p;
-    s.out_cols = (int)Kp;
-    s.e2h = h2 ? &rec[0].e : nullptr;
-    split_planes(s, false, 1, nullptr);  // zero rows past M, zero columns past K
-    s.x = dB + (size_t)z * N * K; s.rows = N;
-    s.out = Bp + (size_t)z * 3 * N * Kp; s.po = (long long)N * Kp; s.out_rows = N;
-    s.e2h = h2 ? &rec[1].e : nullptr;
-    s.frag = bfrag ? 1 : 0;
-    split_planes(s, false, 1, nullptr);
-    s.frag = 0;
-    if (m16) {  // planes of the mask, row stride ld_n, rows_p rows per plane (zeros in the padding)
-      s.x = dmask + (size_t)z * M * N; s.ldx = N; s.rows = M; s.cols = N;
-      s.out = Mp + (size_t)z * 3 * pp; s.ldo = ld_n; s.po = pp; s.out_rows = rows_p; s.out_cols = ld_n;
-      s.e2h = h2 ? &rec[2].e : nullptr;
-      split_planes(s, false, 1, nullptr);
-    }
-  }
-  int rc = 0;
-  if ((rc = sync_rc("split_planes"))) return rc;
-  int slices = 1;
-  if (small) gemm_x3s(g, epi, batch, nullptr);
-  else slices = gemm_x3f(g, epi, batch, nullptr);
-  colsum_finish(d_dbp, N, chunks, batch, d_db, N, nullptr);
-  if ((rc = sync_rc(small ? "gemm_x3s" : "gemm_x3f")) || (rc = gd.check())) return rc;
-  int ec = 0;
-  if (h2 && !gd.back(&ec, &rec[3].e, 1)) return -5;
-  // split launches: the in-launch finish keeps the split row tile, the finishing pass sums shorter chunks
-  info[0] = small ? 3 : slices <= 1 ? 0 : bm == gemm_x3f_split_bm(M, N, (int)Kp, batch) ? 1 : 2;
-  info[1] = bm;
-  info[2] = chunks;
-  info[3] = slices;
-  info[4] = nparts;
-  info[5] = maxrt;
-  info[6] = ec;
-  info[7] = small ? gemm_x3s_ti(M, N, batch) : slices > 1 ? gemm_x3f_split_bm(M, N, (int)Kp, batch) : gemm_x3f_bm(g, batch);
-  if (dC && !gd.back(C, dC, nC)) return -5;
-  // bf16 keeps the high plane only (gemm_x3f leaves the other two alone)
-  const size_t per = (size_t)pp;
-  for (int z = 0; z < batch; ++z) {
-    if (np == 1 && !h2) {
-      std::vector<__bf16> h(per);
-      if (hipMemcpy(h.data(), dCp + (size_t)z * 3 * per, per * 2, hipMemcpyDeviceToHost) != hipSuccess) return -5;
-      for (size_t i = 0; i < per; ++i) Csum[(size_t)z * per + i] = (float)h[i];
-    } else if (!planes_sum(dCp + (size_t)z * 3 * per, 3 * per, per, per, h2, ec, Csum + (size_t)z * per)) {
-      return -5;
-    }
-  }
-  return gd.back(dbp, d_dbp, (size_t)batch * maxrt * N) && gd.back(db, d_db, (size_t)batch * N) ? 0 : -5;
-}
-
-// the k-major x k-major gemm_x3p weight grad with the bias grad finished from column-sum partials
-// (mtsac_debug.h): at once, or through a FinishSink between two unrelated colsum jobs
-int mtsac_debug_wgrad_finish(int mode, int E, int M, int N, int K, int chunks, int splits, const float* A,
-                             const float* B, const float* part, const int* nb, const float* part_pre,
-                             const float* part_post, float* C, float* db, float* db_pre, float* db_post, int* info) {
-  if (mode < 0 || mode > 1 || E < 1 || E > 8 || M < 1 || N < 1 || K < 1 || chunks < 1 || splits < 0 || splits > 64 ||
-      !A || !B || !part || !C || !db || !info || (long long)E * K * std::max(M, N) >= (1LL << 28))
-    return -22;
-  if (mode == 1 && (!nb || !part_pre || !part_post || !db_pre || !db_post || nb[0] < 1 || nb[1] < 1 || nb[2] < 1 ||
-                    nb[3] < 1))
-    return -22;
-  if (hipSetDevice(0) != hipSuccess) return -5;
-  const int Kp = (int)up32(K);
-  long long lda, pa, ldb, pb;
-  plane_geom(M, K, true, lda, pa);
-  plane_geom(N, K, true, ldb, pb);
-  Guarded gd;
-  const float *dA = gd.in(A, (size_t)E * K * M), *dB = gd.in(B, (size_t)E * K * N);
-  const float* dpart = gd.in(part, (size_t)E * chunks * N);
-  __bf16* Ap = gd.mem.get<__bf16>((size_t)3 * pa * E);
-  __bf16* Bp = gd.mem.get<__bf16>((size_t)3 * pb * E);
-  float* dC = gd.out<float>((size_t)E * M * N, "C");
-  float* d_db = gd.out<float>((size_t)E * N, "db");
-  const int want = splits == 0 ? gemm_x3p_splits(M, N, Kp, E, true, 3) : splits;
-  float* ws = gd.mem.get<float>((size_t)std::max(gemm_ws_floats(M, N, E, std::max(want, 2)), 1LL));
-  if (!gd.ok || !Ap || !Bp || !ws) return -12;
-  const float *dpre = nullptr, *dpost = nullptr;
-  float *d_dbpre = nullptr, *d_dbpost = nullptr;
-  if (mode == 1) {
-    dpre = gd.in(part_pre, (size_t)E * nb[0] * nb[1]);
-    dpost = gd.in(part_post, (size_t)E * nb[2] * nb[3]);
-    d_dbpre = gd.out<float>((size_t)E * nb[1], "db_pre");
-    d_dbpost = gd.out<float>((size_t)E * nb[3], "db_post");
-    if (!gd.ok) return -12;
-  }
-  for (int z = 0; z < E; ++z) {
-    split_into(dA + (size_t)z * K * M, M, K, true, Ap + 3 * pa * z);
-    split_into(dB + (size_t)z * K * N, N, K, true, Bp + 3 * pb * z);
-  }
-  SplitGemmParams g{};
-  g.A = Ap; g.lda = lda; g.pA = pa; g.sA = 3 * pa; g.a_kmajor = 1;
-  g.B = Bp; g.ldb = ldb; g.pB = pb; g.sB = 3 * pb; g.b_kmajor = 1;
-  g.C = dC; g.ldc = N; g.sC = (long long)M * N;
-  g.M = M; g.N = N; g.K = Kp;
-  g.splits = splits == 0 ? -1 : splits;
-  g.ws = ws;
-  g.cs_part = dpart; g.cs_chunks = chunks; g.cs_db = d_db; g.cs_sdb = N;
-  // the slices gemm_x3p makes of that request (whole 32-deep K tiles per slice)
-  int S = 1;
-  if (want > 1) {
-    const int kchunk = (Kp / 32 + want - 1) / want * 32;
-    S = (Kp + kchunk - 1) / kchunk;
-  }
-  FinishSink sink;
-  int this_job = -1;
-  if (mode == 1) {
-    sink.job[sink.n++] = colsum_job(dpre, nb[1], nb[0], d_dbpre, nb[1]);
-    g.defer = &sink;
-    this_job = sink.n;
-  }
-  gemm_x3p(g, EPI_STORE, E, nullptr);
-  info[0] = S;
-  info[1] = mode == 1 ? 2 : S > 1 ? 1 : 0;  // who finishes the bias grad: colsum_finish, the reduce launch, finish_many
-  info[2] = mode == 1 ? sink.n : 0;
-  info[3] = mode == 1 && sink.n > this_job ? sink.job[this_job].nred : 0;
-  if (mode == 1) {
-    if (sink.n != this_job + 1) return -5;  // the launcher did not defer its finish
-    sink.job[sink.n++] = colsum_job(dpost, nb[3], nb[2], d_dbpost, nb[3]);
-    info[2] = sink.n;
-    finish_many(sink, E, nullptr);
-  }
-  int rc = 0;
-  if ((rc = sync_rc("wgrad finish")) || (rc = gd.check())) return rc;
-  if (mode == 1 && (!gd.back(db_pre, d_dbpre, (size_t)E * nb[1]) || !gd.back(db_post, d_dbpost, (size_t)E * nb[3])))
-    return -5;
-  return gd.back(C, dC, (size_t)E * M * N) && gd.back(db, d_db, (size_t)E * N) ? 0 : -5;
 }
 
 // the layout kernels alone (mtsac_debug.h): split_planes, transpose_f32, colsum

@@ -45,7 +45,7 @@ int fail(int code, const std::string& msg) {
 
 }  // namespace
 namespace mtsac {
-void set_last_error(const char* msg) { g_last_error = msg; }  // debug.cpp's entry points
+void set_last_error(const char* msg) { g_last_error = msg; }  // debug.cpp's and debug_gemm.cpp's entry points
 }  // namespace mtsac
 namespace {
 
@@ -4232,120 +4232,6 @@ int mtsac_debug_timed_launch(mtsac_engine* h, int32_t i, int32_t* dims, double* 
   float v = 0.f;
   HIP_TRY(hipEventElapsedTime(&v, t.a, t.b));
   *ms = v;
-  return 0;
-}
-
-int mtsac_debug_gemm(int precision, int kind, int epi, int batch, int M, int N, int K, const float* A, int lda, int a_shared,
-                     const float* B, int ldb, float* C, int ldc, const float* bias, const float* mask, int ldm,
-                     float* db) {
-  const int splits = (precision >> 8) & 255;
-  precision &= 255;
-  if (kind < 0 || kind > 2 || batch < 1 || M < 1 || N < 1 || K < 1) return fail(-22, "bad gemm arguments");
-  const bool ta = kind == 2, tb = kind == 1;
-  const long long a_rows = ta ? K : M, b_rows = tb ? N : K;
-  const long long sA = a_rows * lda, sB = b_rows * ldb, sC = (long long)M * ldc;
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *dbias = nullptr, *dmask = nullptr, *ddb = nullptr, *dws = nullptr;
-  auto cleanup = [&]() {
-    for (float* p : {dA, dB, dC, dbias, dmask, ddb, dws})
-      if (p) (void)hipFree(p);
-  };
-  const long long nA = a_shared ? sA : sA * batch;
-  bool ok = hipMalloc(&dA, sizeof(float) * nA) == hipSuccess && hipMalloc(&dB, sizeof(float) * sB * batch) == hipSuccess &&
-            hipMalloc(&dC, sizeof(float) * sC * batch) == hipSuccess;
-  if (ok && bias) ok = hipMalloc(&dbias, sizeof(float) * N * batch) == hipSuccess;
-  if (ok && mask) ok = hipMalloc(&dmask, sizeof(float) * (long long)M * ldm * batch) == hipSuccess;
-  if (ok && db) ok = hipMalloc(&ddb, sizeof(float) * N * batch) == hipSuccess;
-  if (ok && splits > 1) ok = hipMalloc(&dws, sizeof(float) * gemm_ws_floats(M, N, batch, splits)) == hipSuccess;
-  if (!ok) {
-    cleanup();
-    return fail(-12, "hipMalloc failed");
-  }
-  (void)hipMemcpy(dA, A, sizeof(float) * nA, hipMemcpyHostToDevice);
-  (void)hipMemcpy(dB, B, sizeof(float) * sB * batch, hipMemcpyHostToDevice);
-  (void)hipMemcpy(dC, C, sizeof(float) * sC * batch, hipMemcpyHostToDevice);
-  if (bias) (void)hipMemcpy(dbias, bias, sizeof(float) * N * batch, hipMemcpyHostToDevice);
-  if (mask) (void)hipMemcpy(dmask, mask, sizeof(float) * (long long)M * ldm * batch, hipMemcpyHostToDevice);
-  GemmParams g{};
-  g.A = dA; g.lda = lda; g.sA = a_shared ? 0 : sA;
-  g.B = dB; g.ldb = ldb; g.sB = sB;
-  g.C = dC; g.ldc = ldc; g.sC = sC;
-  g.bias = dbias; g.sBias = N;
-  g.mask = dmask; g.ldm = ldm; g.sMask = (long long)M * ldm;
-  g.db = ddb; g.sDb = N;
-  g.M = M; g.N = N; g.K = K;
-  g.splits = splits;
-  g.ws = dws;
-  if (precision == MTSAC_FP32_SPLIT3)
-    gemm_x3(g, (GemmKind)kind, epi, batch, nullptr);
-  else
-    gemm_f32(g, (GemmKind)kind, epi, batch, nullptr);
-  hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(C, dC, sizeof(float) * sC * batch, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && db) e = hipMemcpy(db, ddb, sizeof(float) * N * batch, hipMemcpyDeviceToHost);
-  cleanup();
-  if (e != hipSuccess) return fail(-5, std::string("debug gemm: ") + hipGetErrorString(e));
-  return 0;
-}
-
-__global__ void fill_rand_kernel(float* p, long long n, unsigned seed) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned x = (unsigned)i * 2654435761u ^ seed;
-  x ^= x >> 13; x *= 0x5bd1e995u; x ^= x >> 15;
-  p[i] = ((float)(x & 0xFFFFFF) / 8388608.0f) - 1.0f;
-}
-
-int mtsac_debug_gemm_bench(int precision, int kind, int epi, int batch, int M, int N, int K, int iters,
-                           double* ms_per_launch) {
-  const int splits = (precision >> 8) & 255;
-  precision &= 255;
-  if (kind < 0 || kind > 2 || batch < 1 || M < 1 || N < 1 || K < 1 || iters < 1 || !ms_per_launch)
-    return fail(-22, "bad gemm bench arguments");
-  const bool ta = kind == 2, tb = kind == 1;
-  const int lda = ta ? M : K, ldb = tb ? K : N;
-  const long long sA = (long long)(ta ? K : M) * lda, sB = (long long)(tb ? N : K) * ldb, sC = (long long)M * N;
-  float *A = nullptr, *B = nullptr, *C = nullptr, *bias = nullptr, *db = nullptr, *ws = nullptr;
-  if (splits > 1) HIP_TRY(hipMalloc(&ws, sizeof(float) * gemm_ws_floats(M, N, batch, splits)));
-  HIP_TRY(hipMalloc(&A, sizeof(float) * sA * batch));
-  HIP_TRY(hipMalloc(&B, sizeof(float) * sB * batch));
-  HIP_TRY(hipMalloc(&C, sizeof(float) * sC * batch));
-  HIP_TRY(hipMalloc(&bias, sizeof(float) * N * batch));
-  HIP_TRY(hipMalloc(&db, sizeof(float) * N * batch));
-  for (auto pr : {std::make_pair(A, sA * batch), std::make_pair(B, sB * batch), std::make_pair(C, sC * batch),
-                  std::make_pair(bias, (long long)N * batch)})
-    hipLaunchKernelGGL(fill_rand_kernel, dim3((unsigned)((pr.second + 255) / 256)), dim3(256), 0, nullptr,
-                       pr.first, pr.second, 17u);
-  GemmParams g{};
-  g.A = A; g.lda = lda; g.sA = sA;
-  g.B = B; g.ldb = ldb; g.sB = sB;
-  g.C = C; g.ldc = N; g.sC = sC;
-  g.bias = bias; g.sBias = N;
-  g.mask = C; g.ldm = N; g.sMask = sC;  // any sign pattern will do
-  g.db = (kind == 2) ? db : nullptr; g.sDb = N;
-  g.M = M; g.N = N; g.K = K;
-  g.splits = splits;
-  g.ws = ws;
-  auto launch = [&]() {
-    if (precision == MTSAC_FP32_SPLIT3)
-      gemm_x3(g, (GemmKind)kind, epi, batch, nullptr);
-    else
-      gemm_f32(g, (GemmKind)kind, epi, batch, nullptr);
-  };
-  launch();
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  HIP_TRY(hipEventRecord(e0, nullptr));
-  for (int i = 0; i < iters; ++i) launch();
-  HIP_TRY(hipEventRecord(e1, nullptr));
-  HIP_TRY(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-  *ms_per_launch = ms / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  for (float* p : {A, B, C, bias, db, ws})
-    if (p) (void)hipFree(p);
   return 0;
 }
 
