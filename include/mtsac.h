@@ -147,6 +147,19 @@ const char* mtsac_build_stamp(void);
 void mtsac_default_config(mtsac_config* cfg, int32_t num_tasks);
 
 int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out);
+/* mtsac_create with network flags (mtsac_create is flags = 0).
+ * MTSAC_NET_SHARED_HEAD: actor and critic are the reference's VanillaNetwork -> MLP (mtrl/nn/base.py:11-89):
+ * depth Dense+ReLU layers layer_0 .. layer_{D-1} and ONE Dense head layer_D shared by all tasks (the one-hot
+ * task columns are inputs only).  Parameter, moment and target vectors then use the flax leaf order of that
+ * tree: layer_0/bias, layer_0/kernel, ..., layer_D/bias, layer_D/kernel (critic leaves with the leading ensemble
+ * axis): the head [E](hd,) / [E](W, hd) comes LAST, and the per-task gradient matrices have the same columns.
+ * Every step form, the rollout calls, the per-task gradient pass and the three gradient-surgery modes run on
+ * it; the log slots are unchanged.  -95 with task sharding (task_count < num_tasks); the collective entry
+ * points (mtsac_comm_init with nranks > 1, the hooks) return -95 on such an engine.  DESIGN.md section 17.
+ * mtsac_shared_head: 1 when the engine was created with the flag. */
+#define MTSAC_NET_SHARED_HEAD 1u
+int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, mtsac_engine** out);
+int mtsac_shared_head(const mtsac_engine* h);
 void mtsac_destroy(mtsac_engine* h);
 
 /* parameters / optimizer state, flax leaf order, fp32 */

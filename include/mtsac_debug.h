@@ -188,6 +188,20 @@ int mtsac_debug_head_active_rows(int E, int B, const float* dq, int* n, int* row
 int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W, int hd, const int* task, const float* h,
                               const float* Wh, const float* dout, const float* dq, float* dz, float* dbp, float* db,
                               float* planes, float* dWh, float* dbh, int* counts, int* rows, int* info);
+/* A head shared by all tasks (MTSAC_NET_SHARED_HEAD; HeadParams::shared).
+ * mtsac_debug_head_shared(on): while on, mtsac_debug_head_policy[_noise], _head_critic and _head_backward run
+ * their forward and data-grad kernels with the shared flag -- every row reads block 0 of the Wh / bh passed in,
+ * whatever its task (the per-task weight kernels read no head parameter and are unchanged; head_backward_both
+ * refuses a shared head).  Returns the previous setting.
+ * mtsac_debug_head_backward_shared: Wh [E][W][hd]; the data pass (W % 4 == 0 only; dz [E][B][W] and db [E][W],
+ * rows walked by the per-task lists as in a step) and head_backward_weight_shared: dWh [E][W][hd] =
+ * sum_b h[e][b][w] dout[e][b][o] and dbh [E][hd] = sum_b dout over ALL B rows.  info [8]: 0 whether the data pass
+ * ran, 1 whether the weight pass ran, 2 the self-check's fault word, 3 the weight pass's row chunk R, 4 its
+ * chunk count. */
+int mtsac_debug_head_shared(int on);
+int mtsac_debug_head_backward_shared(int B, int T_l, int E, int W, int hd, const int* task, const float* h,
+                                     const float* Wh, const float* dout, float* dz, float* db, float* dWh, float* dbh,
+                                     int* info);
 /* action_grad: dz1 [E][B][Wc] dense; with dq [E][B] (nullable) the rows are compacted by active_rows' slot
  * first (the dense equivalent has zero rows where dq is 0).  W0 [E][Ic][Wc], cache [B][5A], alpha_w [B];
  * a_data [B][ld_a_data] (nullable) with explore_scale and row_loss_in [B].  Outputs dout [B][2A], row_loss,

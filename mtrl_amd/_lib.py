@@ -31,6 +31,8 @@ LOG_KEYS = (
     "alpha",
 )
 
+NET_SHARED_HEAD = 1  # MTSAC_NET_SHARED_HEAD (mtsac_create_flags)
+
 # enum mtsac_tensor
 ACTOR, CRITIC, CRITIC_TARGET, LOG_ALPHA = 0, 1, 2, 3
 ACTOR_ADAM_MU, ACTOR_ADAM_NU, CRITIC_ADAM_MU, CRITIC_ADAM_NU, ALPHA_ADAM_MU, ALPHA_ADAM_NU = 4, 5, 6, 7, 8, 9
@@ -102,6 +104,8 @@ SIGNATURES = {
     "mtsac_build_stamp": (ctypes.c_char_p, []),
     "mtsac_default_config": (None, [ctypes.POINTER(Config), I32]),
     "mtsac_create": (ctypes.c_int, [ctypes.POINTER(Config), ctypes.c_int, ctypes.POINTER(P)]),
+    "mtsac_create_flags": (ctypes.c_int, [ctypes.POINTER(Config), U32, ctypes.c_int, ctypes.POINTER(P)]),
+    "mtsac_shared_head": (ctypes.c_int, [P]),
     "mtsac_destroy": (None, [P]),
     "mtsac_param_count": (I64, [P, ctypes.c_int]),
     "mtsac_set_params": (ctypes.c_int, [P, ctypes.c_int, P, I64]),
@@ -204,6 +208,8 @@ SIGNATURES = {
     "mtsac_debug_head_critic": (ctypes.c_int, [ctypes.c_int] * 8 + [P] * 13 + [ctypes.c_float] * 2 + [P] * 7),
     "mtsac_debug_head_active_rows": (ctypes.c_int, [ctypes.c_int] * 2 + [P] * 4),
     "mtsac_debug_head_backward": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 14),
+    "mtsac_debug_head_shared": (ctypes.c_int, [ctypes.c_int]),
+    "mtsac_debug_head_backward_shared": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 9),
     "mtsac_debug_head_action_grad": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 6 + [ctypes.c_int] +
                                      [ctypes.c_float] * 3 + [P] * 6),
     "mtsac_debug_head_row_alpha": (ctypes.c_int, [ctypes.c_int] * 5 + [P] * 4),

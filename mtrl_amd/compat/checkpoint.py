@@ -28,6 +28,15 @@ and the opt_state one level deeper, as the reference's chain lays it out:
 (TrainState.params is the whole flax variables dict, hence ``params/params``; the optax
 state nesting follows ``OptimizerConfig.spawn``: see ``opt_prefix``.)
 
+A shared-head agent (``MTSAC.initialize(..., shared_head=True)``: the reference's VanillaNetwork -> MLP,
+mtrl/nn/base.py:11-89, whose head is the last Dense ``layer_D``) writes
+
+    actor/params/params/VanillaNetwork_0/MLP_0/layer_i/{bias,kernel}          i = 0 .. D
+    critic/{params,target_params}/params/VmapQValueFunction_0/VanillaNetwork_0/MLP_0/layer_i/...
+
+with the optimizer state under the same paths (names from flax's auto-naming as read in the reference source;
+not verified against a real orbax checkpoint).
+
 so a converter from a reference orbax tree is a key rename at most.  The engine's flat
 vectors are in ravel_pytree order of exactly these trees (include/mtsac.h), which
 ``to_flax_tree`` / ``from_flax_tree`` make explicit.
@@ -38,13 +47,20 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib as L
-from ..init import leaf_shapes
+from ..init import leaf_shapes, vanilla_leaf_shapes
 
 # params of every TrainState are the flax variables dict, so the collection name comes first
 # (``alpha.params["params"]["log_alpha"]``, mtsac.py:109,720,730; ``critic_state["intermediates"]
 # ["VmapQValueFunction_0"]``, sac.py:419)
 _ACTOR_ROOT = ("params", "MultiHeadNetwork_0")
 _CRITIC_ROOT = ("params", "VmapQValueFunction_0", "MultiHeadNetwork_0")
+_ACTOR_ROOT_VANILLA = ("params", "VanillaNetwork_0", "MLP_0")
+_CRITIC_ROOT_VANILLA = ("params", "VmapQValueFunction_0", "VanillaNetwork_0", "MLP_0")
+
+
+def roots(shared_head: bool) -> tuple[tuple[str, ...], tuple[str, ...]]:
+    """(actor root, critic root) of the parameter trees."""
+    return (_ACTOR_ROOT_VANILLA, _CRITIC_ROOT_VANILLA) if shared_head else (_ACTOR_ROOT, _CRITIC_ROOT)
 
 
 def opt_prefix(max_grad_norm) -> tuple[str, ...]:
@@ -55,17 +71,25 @@ def opt_prefix(max_grad_norm) -> tuple[str, ...]:
     return ("1", "0") if max_grad_norm is not None else ("0",)
 
 
-def _leaf_path(name: str) -> tuple[str, str]:
+def _leaf_path(name: str, shapes=()) -> tuple[str, str]:
+    # the head: VmapDense_0 of the multi-head tree; the Vanilla tree's last Dense, layer_D (its head leaves come last)
+    vanilla = bool(shapes) and shapes[-1][0] == "head_W"
+    head = f"layer_{(len(shapes) - 2) // 2}" if vanilla else "VmapDense_0"
     if name == "head_b":
-        return ("VmapDense_0", "bias")
+        return (head, "bias")
     if name == "head_W":
-        return ("VmapDense_0", "kernel")
+        return (head, "kernel")
     return (f"layer_{name[1:]}", "bias" if name[0] == "b" else "kernel")
 
 
-def network_shapes(kw: dict, which: str):
+def network_shapes(kw: dict, which: str, shared_head: bool = False):
     """Leaf shapes (flat order) of the local actor or critic from engine config kwargs."""
     T = kw.get("task_count", kw["num_tasks"])
+    if shared_head and which == "actor":
+        return vanilla_leaf_shapes(kw["obs_dim"], kw["actor_width"], kw["actor_depth"], 2 * kw["action_dim"], None)
+    if shared_head:
+        return vanilla_leaf_shapes(kw["action_dim"] + kw["obs_dim"], kw["critic_width"], kw["critic_depth"], 1,
+                                   kw["num_critics"])
     if which == "actor":
         return leaf_shapes(kw["obs_dim"], kw["actor_width"], kw["actor_depth"], T, 2 * kw["action_dim"], None)
     return leaf_shapes(kw["action_dim"] + kw["obs_dim"], kw["critic_width"], kw["critic_depth"], T, 1,
@@ -83,9 +107,9 @@ def to_flax_tree(flat: np.ndarray, shapes, root: tuple[str, ...]) -> dict:
     for name, s in shapes:
         n = int(np.prod(s))
         node = tree
-        for k in root + _leaf_path(name)[:-1]:
+        for k in root + _leaf_path(name, shapes)[:-1]:
             node = node.setdefault(k, {})
-        node[_leaf_path(name)[-1]] = flat[off:off + n].reshape(s).copy()
+        node[_leaf_path(name, shapes)[-1]] = flat[off:off + n].reshape(s).copy()
         off += n
     return tree
 
@@ -95,13 +119,13 @@ def from_flax_tree(tree: dict, shapes, root: tuple[str, ...]) -> np.ndarray:
     parts = []
     for name, s in shapes:
         node = tree
-        for k in root + _leaf_path(name):
+        for k in root + _leaf_path(name, shapes):
             if k not in node:
-                raise KeyError(f"missing leaf {'/'.join(root + _leaf_path(name))}")
+                raise KeyError(f"missing leaf {'/'.join(root + _leaf_path(name, shapes))}")
             node = node[k]
         a = np.asarray(node, np.float32)
         if a.shape != tuple(s):
-            raise ValueError(f"leaf {'/'.join(root + _leaf_path(name))}: shape {a.shape}, expected {tuple(s)}")
+            raise ValueError(f"leaf {'/'.join(root + _leaf_path(name, shapes))}: shape {a.shape}, expected {tuple(s)}")
         parts.append(a.reshape(-1))
     return np.concatenate(parts).astype(np.float32)
 
@@ -132,14 +156,15 @@ def _gradnorm_prefix(gradnorm) -> tuple[str, ...]:
     return ("1",) if gradnorm is not None else ()
 
 
-def agent_tree(kw: dict, get, count, key=None, gradnorm=None) -> dict[str, np.ndarray]:
+def agent_tree(kw: dict, get, count, key=None, gradnorm=None, shared_head: bool = False) -> dict[str, np.ndarray]:
     """The MTSAC pytree (mtsac.py:130-151: actor / critic / alpha TrainStates + key) as
     {flax path: array}.  ``get(which)`` returns an engine flat vector (include/mtsac.h ids),
     ``count(i)`` the Adam count of actor (0) / critic (1) / alpha (2).  ``gradnorm``: None, or
     (get_state, inner_clips) with GradNormConfig on both networks -- ``get_state(w)`` the
     ``mtrl_amd.gradnorm.GradNormState`` of the critic (0) / actor (1), ``inner_clips`` their
-    gradnorm_optimizer.max_grad_norm in that order."""
-    ash, csh = network_shapes(kw, "actor"), network_shapes(kw, "critic")
+    gradnorm_optimizer.max_grad_norm in that order.  ``shared_head``: the Vanilla tree (module docstring)."""
+    ash, csh = network_shapes(kw, "actor", shared_head), network_shapes(kw, "critic", shared_head)
+    _ACTOR_ROOT, _CRITIC_ROOT = roots(shared_head)
 
     def state(which_p, which_mu, which_nu, shapes, root, i, clip, extra=None):
         n = np.int32(count(i))
@@ -198,7 +223,8 @@ def agent_state(algo) -> dict[str, np.ndarray]:
     reproduced): [noise seed, draws so far]."""
     eng = algo.engine
     return agent_tree(algo._cfg_kwargs, eng.get_params, eng.get_adam_count, key=algo.noise_key(),
-                      gradnorm=(eng.gradnorm_state, _inner_clips(algo)) if getattr(algo, "gradnorm", False) else None)
+                      gradnorm=(eng.gradnorm_state, _inner_clips(algo)) if getattr(algo, "gradnorm", False) else None,
+                      shared_head=bool(getattr(algo, "shared_head", False)))
 
 
 def _inner_clips(algo) -> tuple:
@@ -206,10 +232,11 @@ def _inner_clips(algo) -> tuple:
                  for c in (algo.config.critic_config, algo.config.actor_config))
 
 
-def load_agent_tree(kw: dict, flat: dict, put, set_count, gradnorm=None) -> None:
+def load_agent_tree(kw: dict, flat: dict, put, set_count, gradnorm=None, shared_head: bool = False) -> None:
     """Inverse of ``agent_tree``: ``put(which, flat_vector)``, ``set_count(i, n)``; ``gradnorm``: None or
     (put_state, inner_clips), ``put_state(w, GradNormState)``."""
-    ash, csh = network_shapes(kw, "actor"), network_shapes(kw, "critic")
+    ash, csh = network_shapes(kw, "actor", shared_head), network_shapes(kw, "critic", shared_head)
+    _ACTOR_ROOT, _CRITIC_ROOT = roots(shared_head)
     a = _unflatten_paths(flat, "actor")
     c = _unflatten_paths(flat, "critic")
     al = _unflatten_paths(flat, "alpha")
@@ -259,6 +286,7 @@ def load_agent_state(algo, flat: dict) -> None:
     """Inverse of ``agent_state``: push every leaf back into the engine."""
     eng = algo.engine
     load_agent_tree(algo._cfg_kwargs, flat, eng.set_params, eng.set_adam_count,
-                    gradnorm=(eng.set_gradnorm_state, _inner_clips(algo)) if getattr(algo, "gradnorm", False) else None)
+                    gradnorm=(eng.set_gradnorm_state, _inner_clips(algo)) if getattr(algo, "gradnorm", False) else None,
+                    shared_head=bool(getattr(algo, "shared_head", False)))
     if "key" in flat:
         algo.set_noise_key(np.asarray(flat["key"]))

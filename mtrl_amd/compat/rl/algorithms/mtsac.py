@@ -8,20 +8,23 @@ Supported: multi-head MLP actor/critic (MultiHeadConfig or VanillaNetworkConfig 
 num_tasks from the algorithm config), MSE critic, Adam optimizers -- the north-star path --
 PCGrad gradient surgery on both networks (PCGradConfig, experiments/misc/mt10_mtmhsac_pcgrad.py) and
 CAGrad or GradNorm on both networks (CAGradConfig, experiments/misc/mt10_mtmhsac_cagrad.py; GradNormConfig,
-experiments/misc/mt10_mtmhsac_gradnorm.py).
+experiments/misc/mt10_mtmhsac_gradnorm.py).  ``MTSAC.initialize(..., shared_head=True)`` (or
+MTSAC_VANILLA_SHARED_HEAD=1) runs a VanillaNetworkConfig as the reference builds it: one head shared by all tasks.
 """
 
 from __future__ import annotations
 
 import dataclasses
+import os
 from collections.abc import Mapping
 
 import numpy as np
 
 from .... import _lib as L
 from ....engine import CAGRAD_LOG_KEYS, GRADNORM_LOG_KEYS, PCGRAD_LOG_KEYS, MTSACEngine, make_config
-from ....init import init_mtsac
+from ....init import init_mtsac, init_vanilla
 from ...config.networks import ContinuousActionPolicyConfig, QValueFunctionConfig
+from ...config.nn import VanillaNetworkConfig
 from ...config.optim import CAGradConfig, GradNormConfig, OptimizerConfig, PCGradConfig
 from ...config.rl import AlgorithmConfig
 from ...config.utils import Activation, Initializer, Optimizer
@@ -84,6 +87,20 @@ def _check_supported(net, what: str):
     if net.optimizer.optimizer is not Optimizer.Adam or split:
         raise NotImplementedError(
             f"{what}: only Adam (optax.adam + clip_by_global_norm), plain or behind PCGrad, CAGrad or GradNorm")
+
+
+def _check_shared_head(net, what: str) -> None:
+    """shared_head: the network config must be the reference's plain VanillaNetwork -> MLP (one head layer_D)."""
+    if not isinstance(net, VanillaNetworkConfig):
+        raise NotImplementedError(
+            f"{what}: shared_head runs the VanillaNetworkConfig tree (one Dense head for all tasks); "
+            f"{type(net).__name__} has its own heads -- give both networks a VanillaNetworkConfig or leave "
+            "shared_head off")
+    if net.use_skip_connections:
+        raise NotImplementedError(f"{what}: shared_head with use_skip_connections: the engine's trunk has no skip "
+                                  "connections")
+    if net.use_layer_norm:
+        raise NotImplementedError(f"{what}: shared_head with use_layer_norm: the engine's trunk has no layer norm")
 
 
 def _check_surgery(config: "MTSACConfig", task_shard, config_cls, name: str, one_network: str, sharded: str,
@@ -196,6 +213,7 @@ class MTSAC(OffPolicyAlgorithm):
         # both optimizers PCGrad, CAGrad or GradNorm ("pcgrad", "cagrad", "gradnorm"): the engine runs the
         # gradient-surgery step with that method's solve
         self.surgery: str | None = None
+        self.shared_head = False  # the engine holds the Vanilla (shared-head) tree (initialize(shared_head=True))
 
     pcgrad = property(lambda self: self.surgery == "pcgrad")
     cagrad = property(lambda self: self.surgery == "cagrad")
@@ -204,14 +222,26 @@ class MTSAC(OffPolicyAlgorithm):
     # ------------------------------------------------------------------ construction
     @staticmethod
     def initialize(config: MTSACConfig, env_config, seed: int = 1, *, precision: str = "split2h",
-                   device: int = 0, task_shard: tuple[int, int] | None = None) -> "MTSAC":
+                   device: int = 0, task_shard: tuple[int, int] | None = None,
+                   shared_head: bool | None = None) -> "MTSAC":
         """task_shard (first task, count): reserved -- this trainer runs unsharded engines (task sharding
-        is driven through mtrl_amd.shard)."""
+        is driven through mtrl_amd.shard).
+
+        shared_head: run a VanillaNetworkConfig as the reference does, VanillaNetwork -> MLP with ONE head
+        layer_D shared by all tasks (the engine's MTSAC_NET_SHARED_HEAD), instead of as the multi-head network.
+        None reads MTSAC_VANILLA_SHARED_HEAD=1 from the environment; default off, so existing scripts and
+        checkpoints keep the multi-head tree.  On, both network configs must be VanillaNetworkConfig without
+        skip connections or layer norm (NotImplementedError otherwise)."""
+        if shared_head is None:
+            shared_head = os.environ.get("MTSAC_VANILLA_SHARED_HEAD") == "1"
         if config.critic_config.use_classification:
             raise NotImplementedError("classification critics are outside the MTSAC MSE path")
         net_a, net_c = config.actor_config.network_config, config.critic_config.network_config
         _check_supported(net_a, "actor")
         _check_supported(net_c, "critic")
+        if shared_head:
+            _check_shared_head(net_a, "actor")
+            _check_shared_head(net_c, "critic")
         surgery = _surgery_mode(config, task_shard)
         if task_shard is not None:
             raise NotImplementedError("task sharding is driven through mtrl_amd.shard, not this trainer")
@@ -230,10 +260,10 @@ class MTSAC(OffPolicyAlgorithm):
             log_std_min=config.actor_config.log_std_min, log_std_max=config.actor_config.log_std_max,
             batch_per_task=128, capacity=128, precision=L.PRECISIONS[precision], noise_seed=seed + 1,
         )
-        eng = MTSACEngine(make_config(**kw), device=device)
+        eng = MTSACEngine(make_config(**kw), device=device, shared_head=bool(shared_head))
         _switch_on(eng, config, surgery)
-        a, q = init_mtsac(T, obs_dim, act_dim, net_a.width, net_a.depth, net_c.width, net_c.depth,
-                          config.num_critics, seed=seed)
+        a, q = (init_vanilla if shared_head else init_mtsac)(T, obs_dim, act_dim, net_a.width, net_a.depth, net_c.width,
+                                                             net_c.depth, config.num_critics, seed=seed)
         eng.set_params(L.ACTOR, a)
         eng.set_params(L.CRITIC, q)
         eng.set_params(L.CRITIC_TARGET, q)
@@ -241,6 +271,7 @@ class MTSAC(OffPolicyAlgorithm):
         print("Critic Params:", eng.param_count(L.CRITIC))
         agent = MTSAC(config, env_config, seed, eng, kw)
         agent.surgery = surgery
+        agent.shared_head = bool(shared_head)
         return agent
 
     def _rebuild(self, **changes) -> None:
@@ -256,7 +287,7 @@ class MTSAC(OffPolicyAlgorithm):
         gn_state = [self.engine.gradnorm_state(w) for w in range(2)] if self.gradnorm else []
         self._cfg_kwargs.update(changes)
         old = self.engine
-        self.engine = MTSACEngine(make_config(**self._cfg_kwargs), device=old.device)
+        self.engine = MTSACEngine(make_config(**self._cfg_kwargs), device=old.device, shared_head=self.shared_head)
         old.close()
         _switch_on(self.engine, self.config, self.surgery, gn_state)
         for w, v in keep.items():

@@ -193,10 +193,10 @@ __global__ void sum_parts_kernel(const double* __restrict__ part, int nparts, in
 
 __global__ void scatter_blocks_kernel(const float* __restrict__ src, long long src_off, long long src_ms,
                                       float* __restrict__ dst, long long P, long long dst_off, long long dst_ms, int E,
-                                      int T, long long blk) {
+                                      int T, long long blk, long long dst_tblk) {
   const int e = blockIdx.z, t = blockIdx.y;
   const float* s = src + src_off + e * src_ms + t * blk;
-  float* d = dst + (long long)t * P + dst_off + e * dst_ms + t * blk;
+  float* d = dst + (long long)t * P + dst_off + e * dst_ms + t * dst_tblk;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < blk; i += (long long)gridDim.x * blockDim.x)
     d[i] = s[i];
 }
@@ -242,10 +242,11 @@ void task_pair_stats(const float* G, int T, long long P, const float* thr /*devi
 }
 
 void scatter_task_blocks(const float* src, long long src_off, long long src_ms, float* dst, long long P,
-                         long long dst_off, long long dst_ms, int E, int T, long long blk, hipStream_t st) {
+                         long long dst_off, long long dst_ms, int E, int T, long long blk, hipStream_t st,
+                         bool tied) {
   const int bx = (int)std::min<long long>((blk + 255) / 256, 64);
   hipLaunchKernelGGL(scatter_blocks_kernel, dim3(bx, T, E), dim3(256), 0, st, src, src_off, src_ms, dst, P, dst_off,
-                     dst_ms, E, T, blk);
+                     dst_ms, E, T, blk, tied ? 0LL : blk);
 }
 
 void check_interleaved(const int* task, int B, int T_l, int* err, hipStream_t st) {

@@ -218,6 +218,15 @@ int mtsac_debug_head_bwd_split(int mode) {
   return old;
 }
 
+// 1: the head entry points below run their forward and data-grad kernels with HeadParams::shared set (every row
+// reads block 0 of Wh / bh, whatever its task); the per-task weight kernels read no head parameter and stay
+static int g_dbg_head_shared = 0;
+int mtsac_debug_head_shared(int on) {
+  const int old = g_dbg_head_shared;
+  g_dbg_head_shared = on ? 1 : 0;
+  return old;
+}
+
 // eps given: injected noise; eps null: the device stream (seed, stream_id + s for row set s, counter, noise_div)
 static int head_policy_run(int form, int flags, int B, int T_l, int W, int A, int ld_a, const int* task, const float* h,
                            const float* Wh, const float* bh, const float* eps, unsigned long long seed,
@@ -255,7 +264,7 @@ static int head_policy_run(int form, int flags, int B, int T_l, int W, int A, in
   for (int s = 0; s < ns; ++s) {
     PolicyParams p{};
     p.head.h = d_h + (size_t)s * B * W; p.head.Wh = d_Wh; p.head.WhT = d_WhT; p.head.bh = d_bh; p.head.task = tl.d_task;
-    p.head.B = B; p.head.W = W; p.head.hd = hd; p.head.E = 1;
+    p.head.B = B; p.head.W = W; p.head.hd = hd; p.head.E = 1; p.head.shared = g_dbg_head_shared;
     p.eps = d_eps ? d_eps + (size_t)s * B * A : nullptr;
     p.seed = seed; p.counter = d_counter; p.stream_id = stream_id + (unsigned)s; p.noise_div = noise_div;
     p.A = A; p.ls_min = ls_min; p.ls_max = ls_max;
@@ -318,7 +327,7 @@ int mtsac_debug_head_critic(int mode, int flags, int B, int T_l, int E, int W, i
   auto head = [&](const float* hh, const float* ww, const float* bb) {
     HeadParams q{};
     q.h = g.in(hh, nh); q.Wh = g.in(ww, nw); q.bh = g.in(bb, nb); q.task = d_task;
-    q.B = B; q.W = W; q.hd = 1; q.E = E;
+    q.B = B; q.W = W; q.hd = 1; q.E = E; q.shared = g_dbg_head_shared;
     q.sWh = (long long)T_l * W; q.sbh = T_l; q.sh = (long long)B * W;
     return q;
   };
@@ -449,7 +458,7 @@ int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W,
   TaskLists tl = make_lists(g, task, B, T_l);
   HeadParams hp{};
   hp.h = g.in(h, nh); hp.Wh = g.in(Wh, nw); hp.task = tl.d_task;
-  hp.B = B; hp.W = W; hp.hd = hd; hp.E = E;
+  hp.B = B; hp.W = W; hp.hd = hd; hp.E = E; hp.shared = g_dbg_head_shared;
   hp.sWh = (long long)T_l * W * hd; hp.sbh = (long long)T_l * hd; hp.sh = (long long)B * W;
   hp.fault = g.mem.get<unsigned>(1);  // zeroed
   const float* d_dout = g.in(dout, nd);
@@ -513,6 +522,51 @@ int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W,
   return g.back(dz, d_dz, nh) && g.back(dbp, d_dbp, (size_t)E * chunks * W) && g.back(db, d_db, (size_t)E * W) &&
                  g.back(dWh, d_dWh, nw) && g.back(dbh, d_dbh, (size_t)E * T_l * hd) &&
                  g.back(counts, tl.counts, (size_t)T_l) && g.back(rows, tl.rows, (size_t)T_l * B)
+             ? 0
+             : -5;
+}
+
+int mtsac_debug_head_backward_shared(int B, int T_l, int E, int W, int hd, const int* task, const float* h,
+                                     const float* Wh, const float* dout, float* dz, float* db, float* dWh, float* dbh,
+                                     int* info) {
+  if (!head_kernels_cover(hd, W) || E < 1 || E > 4 || W < 1 || !h || !Wh || !dout || !dz || !db || !dWh || !dbh || !info ||
+      !tasks_ok(task, B, T_l) || (long long)E * B * W >= (1LL << 28) || !outputs_distinct({dz, db, dWh, dbh, info}))
+    return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const int chunks = head_backward_chunks(T_l);
+  const size_t nh = (size_t)E * B * W, nw = (size_t)E * W * hd, nd = (size_t)E * B * hd;
+  Guarded g;
+  TaskLists tl = make_lists(g, task, B, T_l);
+  HeadParams hp{};
+  hp.h = g.in(h, nh); hp.Wh = g.in(Wh, nw); hp.task = tl.d_task;
+  hp.B = B; hp.W = W; hp.hd = hd; hp.E = E; hp.shared = 1;
+  hp.sWh = (long long)W * hd; hp.sbh = hd; hp.sh = (long long)B * W;
+  hp.fault = g.mem.get<unsigned>(1);  // zeroed
+  const float* d_dout = g.in(dout, nd);
+  float* d_dz = g.out<float>(nh, "dz");
+  float* d_dbp = g.out<float>((size_t)E * chunks * W, "dbp");
+  float* d_db = g.out<float>((size_t)E * W, "db");
+  float* d_ws = g.out<float>((size_t)head_shared_ws_floats(B, W, hd, E), "ws");
+  float* d_dWh = g.out<float>(nw, "dWh");
+  float* d_dbh = g.out<float>((size_t)E * hd, "dbh");
+  if (!g.ok || !hp.fault) return -12;
+  std::fill(info, info + 8, 0);
+  const bool data = W % 4 == 0;  // the data pass's contract (kernels.h)
+  if (data) {
+    head_backward_data(hp, d_dout, (long long)B * hd, d_dz, tl.counts, tl.rows, B, T_l, nullptr, PlaneOut{}, d_dbp);
+    colsum_finish(d_dbp, W, chunks, E, d_db, W, nullptr);
+  }
+  info[0] = data ? 1 : 0;
+  info[1] = head_backward_weight_shared(hp, d_dout, (long long)B * hd, d_ws, d_dWh, d_dbh, nullptr) ? 1 : 0;
+  info[3] = HEAD_SHARED_ROWS;
+  info[4] = head_shared_chunks(B);
+  int rc = 0;
+  if ((rc = sync_rc("head_backward_shared")) || (rc = g.check())) return rc;
+  unsigned fault = 0;
+  if (!g.back(&fault, hp.fault, 1)) return -5;
+  info[2] = (int)fault;
+  return g.back(dz, d_dz, nh) && g.back(db, d_db, (size_t)E * W) && g.back(dWh, d_dWh, nw) &&
+                 g.back(dbh, d_dbh, (size_t)E * hd)
              ? 0
              : -5;
 }

@@ -65,6 +65,21 @@ long long align_up(long long x, long long a) { return (x + a - 1) / a * a; }
 
 struct Net {
   int in_dim = 0, in_ld = 0, width = 0, depth = 0, T_l = 0, hd = 0, E = 1;
+  // shared: ONE head for all tasks (the Vanilla network's layer_D, MTSAC_NET_SHARED_HEAD).  The device layout
+  // keeps the head region in front of trunk_off with Th = 1 head block instead of T_l, so the clip norm, the
+  // fused Adam, Polyak, the weight records (amax[1] = max |head|) and the transposed copy treat it as the
+  // heads of a one-task network; only the flax leaf order (leaves / dense) differs: layer_0 .. layer_D, the
+  // head last.
+  bool shared = false;
+  int Th = 0;  // head blocks stored: T_l, or 1 (shared)
+  // leaf indices in the flax order (leaves / dense)
+  int lk_hb() const { return shared ? 2 * depth : 0; }
+  int lk_hW() const { return shared ? 2 * depth + 1 : 1; }
+  int lk_b(int i) const { return shared ? 2 * i : 2 + 2 * i; }
+  int lk_W(int i) const { return shared ? 2 * i + 1 : 3 + 2 * i; }
+  // shared: the row-chunk partials of the head's weight grad (head_backward_weight_shared), and the per-task
+  // head grads of the task-gradient pass ([E][T_l][W hd] then [E][T_l][hd]; allocated with the [T][P] matrices)
+  float *hws = nullptr, *tgh = nullptr;
   long long off_hb = 0, off_hW = 0, off_b[MAXD] = {}, off_W[MAXD] = {};
   long long ms_hb = 0, ms_hW = 0, ms_b = 0, ms_W[MAXD] = {};  // member strides
   long long n_flat = 0, trunk_off = 0, n_params = 0;
@@ -119,8 +134,11 @@ struct Net {
   float *gparts = nullptr, *hparts = nullptr, *pph = nullptr, *ppt = nullptr;
   int n_pph = 0, n_ppt = 0;
 
-  void layout(int in, int in_ld_, int W, int D, int T, int hd_, int E_) {
+  void layout(int in, int in_ld_, int W, int D, int T, int hd_, int E_, bool shared_) {
     in_dim = in; in_ld = in_ld_; width = W; depth = D; T_l = T; hd = hd_; E = E_;
+    shared = shared_;
+    Th = shared ? 1 : T;
+    T = Th;
     long long o = 0;
     auto leaf = [&](long long member, long long& off, long long& ms) {
       off = o;
@@ -139,6 +157,7 @@ struct Net {
       fan = W;
     }
     n_flat = o;
+    if (shared) std::rotate(leaves.begin(), leaves.begin() + 2, leaves.end());  // the head's leaves last
     dense.assign(1, 0);
     for (const auto& lf : leaves) dense.push_back(dense.back() + lf.second);
   }
@@ -945,12 +964,12 @@ struct mtsac_engine {
   // (one predicate for both sides of the hand-off: refresh_wt skips head_transpose exactly when
   // optimize() gives the head pass AdamParams::whT, whose range must lie inside the heads' part)
   bool whT_fused(const Net& net) const {
-    const long long n = (long long)T_l * net.width * net.hd;
+    const long long n = (long long)net.Th * net.width * net.hd;
     return net.whT && net.E == 1 && net.off_hW % 4 == 0 && n % 4 == 0 && net.off_hW + n <= net.trunk_off;
   }
   void refresh_wt(Net& net, const float* params, int which, hipStream_t s, bool fused = false) {
     if (which == 0 && net.whT && net.E == 1 && !(fused && whT_fused(net)))
-      head_transpose(params + net.off_hW, T_l, net.width, net.hd, net.whT, s);
+      head_transpose(params + net.off_hW, net.Th, net.width, net.hd, net.whT, s);
     if (fused && tiles_fusable(net)) return;  // the optimizer wrote every plane the GEMMs read
     for (int i = planes ? 0 : 1; i < net.depth; ++i) {
       if (!planes) {
@@ -1098,7 +1117,15 @@ struct mtsac_engine {
     hp.sbh = net.ms_hb;
     hp.sh = (long long)M * net.width;
     hp.fault = reinterpret_cast<unsigned*>(err + 1);  // err[1]: the head backward self-check word (check_err)
+    hp.shared = net.shared ? 1 : 0;
     return hp;
+  }
+  // the head's weight and bias grad into Net::g: per task (row lists), or over all rows (a shared head)
+  void head_wgrad(Net& net, const HeadParams& hp, const float* dout, long long s_dout) {
+    if (net.shared)
+      head_backward_weight_shared(hp, dout, s_dout, net.hws, net.g + net.off_hW, net.g + net.off_hb, cur);
+    else
+      head_backward_weight(hp, dout, s_dout, counts, rows, B, net.g + net.off_hW, net.g + net.off_hb, cur);
   }
 
   void allreduce(float* buf, size_t count) { coll(0, buf, count); }
@@ -1340,7 +1367,7 @@ struct mtsac_engine {
     if (whT_fused(net)) {
       a.whT = net.whT;
       a.whT_b4 = net.off_hW / 4;
-      a.whT_e4 = (net.off_hW + (long long)T_l * net.width * net.hd) / 4;
+      a.whT_e4 = (net.off_hW + (long long)net.Th * net.width * net.hd) / 4;
       a.whT_W = net.width;
       a.whT_hd = net.hd;
     }
@@ -1721,8 +1748,7 @@ struct mtsac_engine {
       }
     });
     const int s_chw = seg({s_cl}, 3, [&] {
-      if (!c_both)
-        head_backward_weight(chp, dq, Bl, counts, rows, Bl, critic.g + critic.off_hW, critic.g + critic.off_hb, cur);
+      if (!c_both) head_wgrad(critic, chp, dq, Bl);
     });
     int s_afs = s_af;
     const int s_cb = backward_segs(critic, critic.p, xc, ld_c, hc, hcp, dzc, dzcp, s_cl, s_chw, Bl, [&] {
@@ -1780,10 +1806,9 @@ struct mtsac_engine {
     if (pipelined) (void)hipEventRecord(ev_ap[step_par], segs[s_ap].lane);
     const HeadParams ahp = head(actor, actor.p, ha[actor.depth - 1], Bl, task);
     // the head's data and weight passes in one launch (head_bwd_both's conditions)
-    const bool a_both = top_planes(actor, dzap).p != nullptr && actor.width % 4 == 0;
+    const bool a_both = top_planes(actor, dzap).p != nullptr && actor.width % 4 == 0 && !actor.shared;
     const int s_ahw = seg({s_ap}, 3, [&] {
-      if (!a_both)
-        head_backward_weight(ahp, dout_a, 0, counts, rows, Bl, actor.g + actor.off_hW, actor.g + actor.off_hb, cur);
+      if (!a_both) head_wgrad(actor, ahp, dout_a, 0);
     });
     const int s_ad = seg({s_ap}, 1, [&] {
       if (!(a_both && head_bwd_both(actor, ahp, dout_a, 0, dzap, true))) head_bwd(actor, ahp, dout_a, 0, dza, dzap, true);
@@ -1840,6 +1865,9 @@ struct mtsac_engine {
       const Net& net = w == 0 ? critic : actor;
       tgP[w] = net.n_params;
       if (!tg[w] && (rc = alloc(&tg[w], (size_t)T_l * tgP[w]))) return rc;
+      Net& nw = w == 0 ? critic : actor;
+      if (nw.shared && !nw.tgh && (rc = alloc(&nw.tgh, (size_t)nw.E * T_l * ((size_t)nw.width * nw.hd + nw.hd))))
+        return rc;
     }
     if (!sel_prefix) {
       if ((rc = alloc(&sel_prefix, 2 * 64)) || (rc = alloc(&sel_rank, 2 * 64)) || (rc = alloc(&sel_hist, 512 * 64)) ||
@@ -1865,10 +1893,10 @@ struct mtsac_engine {
       g.B = dz[i] + (long long)e * B * net.width;
       g.ldb = net.width * T_l;
       g.sB = net.width;
-      g.C = tg[w] + off[3 + 2 * i] + (long long)e * fan * net.width;
+      g.C = tg[w] + off[net.lk_W(i)] + (long long)e * fan * net.width;
       g.ldc = net.width;
       g.sC = tgP[w];
-      g.db = tg[w] + off[2 + 2 * i] + (long long)e * net.width;
+      g.db = tg[w] + off[net.lk_b(i)] + (long long)e * net.width;
       g.sDb = tgP[w];
       g.M = fan;
       g.N = net.width;
@@ -1881,10 +1909,31 @@ struct mtsac_engine {
   // the task's own head block (bias, kernel) of the padded gradient buffer into its dense row
   void task_heads(Net& net, int w) {
     const std::vector<long long>& off = net.dense;
+    if (net.shared) {  // row t takes task t's gradient of the ONE head (Net::tgh) at the head's own columns
+      const long long nw = (long long)net.width * net.hd;
+      scatter_task_blocks(net.tgh, (long long)net.E * T_l * nw, (long long)T_l * net.hd, tg[w], tgP[w],
+                          off[net.lk_hb()], net.hd, net.E, T_l, net.hd, cur, true);
+      scatter_task_blocks(net.tgh, 0, T_l * nw, tg[w], tgP[w], off[net.lk_hW()], nw, net.E, T_l, nw, cur, true);
+      return;
+    }
     scatter_task_blocks(net.g, net.off_hb, net.ms_hb, tg[w], tgP[w], off[0], (long long)T_l * net.hd, net.E, T_l,
                         net.hd, cur);
     scatter_task_blocks(net.g, net.off_hW, net.ms_hW, tg[w], tgP[w], off[1], (long long)T_l * net.width * net.hd,
                         net.E, T_l, (long long)net.width * net.hd, cur);
+  }
+  // the per-task head weight and bias grads of the task-gradient pass: every task's own block of Net::g, or
+  // (a shared head) per-task blocks in Net::tgh -- the per-task kernel writes [E][T_l] blocks at the strides
+  // it is given and reads no head parameter
+  void task_head_wgrad(Net& net, HeadParams hp, const float* dout, long long s_dout) {
+    if (!net.shared) {
+      head_backward_weight(hp, dout, s_dout, counts, rows, B, net.g + net.off_hW, net.g + net.off_hb, cur);
+      return;
+    }
+    const long long nw = (long long)net.width * net.hd;
+    hp.shared = 0;
+    hp.sWh = T_l * nw;
+    hp.sbh = (long long)T_l * net.hd;
+    head_backward_weight(hp, dout, s_dout, counts, rows, B, net.tgh, net.tgh + (long long)net.E * T_l * nw, cur);
   }
 
   // the batch into the input buffers, its row lists; rows must be interleaved i*T + t
@@ -1954,7 +2003,7 @@ struct mtsac_engine {
       critic_head(c, cur);
     }
     head_backward_data(chp, dq, Bl, dzc[Dc - 1], counts, rows, Bl, T_l, cur);
-    head_backward_weight(chp, dq, Bl, counts, rows, Bl, critic.g + critic.off_hW, critic.g + critic.off_hb, cur);
+    task_head_wgrad(critic, chp, dq, Bl);
     task_heads(critic, 0);
     for (int i = Dc - 1; i >= 0; --i) {
       task_wgrad(critic, 0, xc, ld_c, hc, dzc, i);
@@ -2004,7 +2053,7 @@ struct mtsac_engine {
     }
     const HeadParams ahp = head(actor, actor.p, ha[Da - 1], Bl, task);
     head_backward_data(ahp, dout_a, 0, dza[Da - 1], counts, rows, Bl, T_l, cur);
-    head_backward_weight(ahp, dout_a, 0, counts, rows, Bl, actor.g + actor.off_hW, actor.g + actor.off_hb, cur);
+    task_head_wgrad(actor, ahp, dout_a, 0);
     task_heads(actor, 1);
     for (int i = Da - 1; i >= 0; --i) {
       task_wgrad(actor, 1, xa, ld_a, ha, dza, i);
@@ -2367,6 +2416,7 @@ struct mtsac_engine {
   // the other tasks' head blocks of every row stay zero: only the rows' head ranges are cleared (the
   // trunk leaves are stored whole by the per-task weight grads)
   void clear_task_heads(const Net& net, int w) {
+    if (net.shared) return;  // every row's head columns are written (task_heads)
     (void)hipMemset2DAsync(tg[w], sizeof(float) * tgP[w], 0, sizeof(float) * net.dense[2], T_l, cur);
   }
 
@@ -2569,12 +2619,26 @@ int pcg_jump_table(unsigned long long* out /* 65*4 */) {
 }
 
 int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
+  return mtsac_create_flags(cfg, 0, hip_device, out);
+}
+
+int mtsac_shared_head(const mtsac_engine* h) {
+  if (!h) return fail(-22, "null engine");
+  return h->actor.shared ? 1 : 0;
+}
+
+int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, mtsac_engine** out) {
   if (!cfg || !out) return fail(-22, "null argument");
   *out = nullptr;
   const mtsac_config& c = *cfg;
+  if (flags & ~(uint32_t)MTSAC_NET_SHARED_HEAD) return fail(-22, "unknown creation flag");
+  const bool shared = (flags & MTSAC_NET_SHARED_HEAD) != 0;
   if (c.num_tasks < 1 || c.task_count < 1 || c.task_begin < 0 || c.task_begin + c.task_count > c.num_tasks)
     return fail(-22, "invalid task range");
   if (c.task_count > 64) return fail(-22, "at most 64 tasks per engine");
+  if (shared && c.task_count != c.num_tasks)
+    return fail(-95, "a shared head on a task-sharded engine is not supported: its gradient would have to join the "
+                     "trunk's all-reduce buckets and the sharded optimizer");
   if (c.num_tasks > EXTRA - 8) return fail(-22, "num_tasks too large");
   if (c.action_dim < 1 || c.action_dim > 64) return fail(-22, "action_dim must be in [1, 64]");
   if (c.obs_dim < c.num_tasks) return fail(-22, "obs_dim must include the one-hot task id");
@@ -2661,9 +2725,11 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
     e->evpool.push_back(ev);
   }
 
-  e->actor.layout(e->D, e->ld_a, c.actor_width, c.actor_depth, e->T_l, 2 * e->A, 1);
-  e->critic.layout(e->D + e->A, e->ld_c, c.critic_width, c.critic_depth, e->T_l, 1, c.num_critics);
+  e->actor.layout(e->D, e->ld_a, c.actor_width, c.actor_depth, e->T_l, 2 * e->A, 1, shared);
+  e->critic.layout(e->D + e->A, e->ld_c, c.critic_width, c.critic_depth, e->T_l, 1, c.num_critics, shared);
   for (Net* net : {&e->actor, &e->critic}) {
+    if (shared && (rc = e->alloc(&net->hws, (size_t)head_shared_ws_floats(e->B, net->width, net->hd, net->E))))
+      return bad(rc);
     if ((rc = e->alloc(&net->p, net->n_flat))) return bad(rc);
     if ((rc = e->alloc(&net->g, net->n_flat + EXTRA))) return bad(rc);
     if ((rc = e->alloc(&net->m, net->n_flat))) return bad(rc);
@@ -2739,7 +2805,7 @@ int mtsac_create(const mtsac_config* cfg, int hip_device, mtsac_engine** out) {
         if (net->x3f && (rc = e->alloc(&net->wtp[w][i], (size_t)net->E * 3 * net->wtps(i)))) return bad(rc);
       }
     if (net == &e->actor && net->E == 1 && net->width % 4 == 0 &&
-        (rc = e->alloc(&net->whT, (size_t)e->T_l * net->width * net->hd)))
+        (rc = e->alloc(&net->whT, (size_t)net->Th * net->width * net->hd)))
       return bad(rc);
   }
   e->Ma = (int)(e->actor.krows + e->B);
@@ -3914,6 +3980,7 @@ int mtsac_comm_init_timeout(mtsac_engine* h, const void* unique_id, int32_t nran
   if (!h || !unique_id) return fail(-22, "null argument");
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(-22, "bad rank / nranks");
   if (h->comm) return fail(-16, "communicator already initialised");
+  if (h->actor.shared && nranks > 1) return fail(-95, "a shared head's gradient is in no collective: shared-head engines run on one GPU");
   ncclUniqueId id;
   std::memcpy(&id, unique_id, sizeof(id));
   HIP_TRY(hipSetDevice(h->device));
@@ -3986,6 +4053,7 @@ int mtsac_comm_nranks(mtsac_engine* h, int32_t* nranks) {
 
 int mtsac_set_allreduce_hook(mtsac_engine* h, mtsac_allreduce_fn fn, void* user) {
   if (!h) return fail(-22, "null engine");
+  if (fn && h->actor.shared) return fail(-95, "a shared head's gradient is in no collective: shared-head engines run on one GPU");
   h->hook = fn;
   h->hook_user = user;
   if (fn) h->chook = nullptr;
@@ -3995,6 +4063,7 @@ int mtsac_set_allreduce_hook(mtsac_engine* h, mtsac_allreduce_fn fn, void* user)
 int mtsac_set_collective_hook(mtsac_engine* h, mtsac_collective_fn fn, void* user, int32_t rank, int32_t world) {
   if (!h) return fail(-22, "null engine");
   if (fn && (world < 1 || rank < 0 || rank >= world)) return fail(-22, "bad rank / world");
+  if (fn && h->actor.shared) return fail(-95, "a shared head's gradient is in no collective: shared-head engines run on one GPU");
   h->chook = fn;
   h->chook_user = user;
   h->hook_rank = fn ? rank : 0;
@@ -4067,6 +4136,7 @@ int mtsac_debug_set_collective_model(mtsac_engine* h, int32_t nranks, double bus
   if (!h) return fail(-22, "null engine");
   if (h->comm || h->hook || h->chook) return fail(-16, "a communicator or collective hook is installed");
   if (nranks < 1 || (nranks > 1 && !(bus_gbps > 0.0))) return fail(-22, "nranks >= 1 and bus_gbps > 0");
+  if (nranks > 1 && h->actor.shared) return fail(-95, "a shared head's gradient is in no collective: shared-head engines run on one GPU");
   HIP_TRY(hipStreamSynchronize(h->st));
   h->cmodel.nranks = nranks;
   h->cmodel.gbps = bus_gbps;

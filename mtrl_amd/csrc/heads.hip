@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void policy_head_kernel(PolicyParams p) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   const HeadParams& hp = p.head;
   if (b >= hp.B) return;
-  const int t = hp.task[b];
+  const int t = hp.shared ? 0 : hp.task[b];  // the head's block (a shared head has one)
   float acc[HD];
   {
     const float* const hr[1] = {hp.h + (long long)b * hp.W};
@@ -241,11 +241,12 @@ __device__ inline void policy_head_grouped_body(const PolicyParams& p) {
     hr[r] = hp.h + (long long)row[r] * hp.W;
   }
   float acc[RW][HD];
-  rows_dot<HD, RW>(hr, hp.Wh + (long long)t * hp.W * HD, hp.W, acc,
-                   hp.WhT ? hp.WhT + (long long)t * hp.W * HD : nullptr);
+  const int th = hp.shared ? 0 : t;  // the head's block (a shared head has one)
+  rows_dot<HD, RW>(hr, hp.Wh + (long long)th * hp.W * HD, hp.W, acc,
+                   hp.WhT ? hp.WhT + (long long)th * hp.W * HD : nullptr);
 #pragma unroll
   for (int r = 0; r < RW; ++r)
-    if (j0 + wave * RW + r < n) policy_finish<HD>(p, row[r], t, acc[r], lane);
+    if (j0 + wave * RW + r < n) policy_finish<HD>(p, row[r], th, acc[r], lane);
 }
 
 template <int HD, int RW>
@@ -285,20 +286,22 @@ __global__ __launch_bounds__(256) void critic_head_kernel(CriticHeadParams p) {
   float dqmax = 0.f;
   for (int b = wid; b < hp.B; b += gridDim.x * 4) {
   const int t = hp.task[b];
+  const int th = hp.shared ? 0 : t;  // the head's block (a shared head has one)
   float q[4];
   const int E = hp.E;
   for (int e = 0; e < E; ++e) {
     float acc[1];
-    head_dot<1>(hp.h + e * hp.sh + (long long)b * hp.W, hp.Wh + e * hp.sWh + (long long)t * hp.W, hp.W, acc);
-    q[e] = acc[0] + hp.bh[e * hp.sbh + t];
+    head_dot<1>(hp.h + e * hp.sh + (long long)b * hp.W, hp.Wh + e * hp.sWh + (long long)th * hp.W, hp.W, acc);
+    q[e] = acc[0] + hp.bh[e * hp.sbh + th];
   }
   float qt[4];  // fused_target: the target critic's heads of the same row (same row, same task)
   if (p.fused_target) {
     const HeadParams& th = p.thead;
+    const int tt = th.shared ? 0 : t;
     for (int e = 0; e < E; ++e) {
       float acc[1];
-      head_dot<1>(th.h + e * th.sh + (long long)b * th.W, th.Wh + e * th.sWh + (long long)t * th.W, th.W, acc);
-      qt[e] = acc[0] + th.bh[e * th.sbh + t];
+      head_dot<1>(th.h + e * th.sh + (long long)b * th.W, th.Wh + e * th.sWh + (long long)tt * th.W, th.W, acc);
+      qt[e] = acc[0] + th.bh[e * th.sbh + tt];
     }
   }
   if (lane != 0) continue;
@@ -478,7 +481,7 @@ __device__ inline void head_bwd_data_body(const HeadParams& hp, const float* __r
   const int* rw = rows + (long long)t * max_rows;
   float wt[4][HD];
   if (ok) {
-    const float* Wt = hp.Wh + e * hp.sWh + ((long long)t * hp.W + w) * HD;
+    const float* Wt = hp.Wh + e * hp.sWh + ((long long)(hp.shared ? 0 : t) * hp.W + w) * HD;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -761,6 +764,142 @@ __global__ __launch_bounds__(256) void head_bwd_weight_inject_kernel(HeadParams 
                                  blockIdx.z, red, chk);
 }
 
+// ------------------------------------------------------------------ shared head: weight and bias grad
+// One head for all tasks (HeadParams::shared): the sums run over ALL rows, so the rows are tiled instead
+// of the tasks.  Block (row chunk c, 256 columns, member e): wave g adds the chunk's rows r0 + g, r0 + g + 4,
+// ... in order, the four waves are added in order (head_bwd_weight_body's association, self-checked the
+// same way), and the chunk's partial goes to ws_w[e][c][w][o]; the column-tile-0 blocks also leave the
+// chunk's sum of dout in ws_b[e][c][o] (one wave, a row per lane, the fixed butterfly of wsum).  The chunks
+// are added in ascending order by head_shared_finish_kernel.  No list, no atomics: one order per shape.
+template <int HD>
+__device__ inline void head_shared_bias(const float* __restrict__ d, int r0, int r1, float* __restrict__ out) {
+  static_assert(HEAD_SHARED_ROWS == 64, "a chunk's rows map to one wave's lanes");
+  if (threadIdx.x >= 64) return;
+  const int row = r0 + (int)threadIdx.x;
+#pragma unroll
+  for (int o = 0; o < HD; ++o) {
+    const float s = wsum(row < r1 ? d[(long long)row * HD + o] : 0.f);
+    if (threadIdx.x == 0) out[o] = s;
+  }
+}
+
+template <int HD>
+__global__ __launch_bounds__(256) void head_bwd_weight_shared_kernel(HeadParams hp, const float* __restrict__ dout,
+                                                                     long long s_dout, float* __restrict__ ws_w,
+                                                                     float* __restrict__ ws_b) {
+  __shared__ float4 red[HD][4][64];
+  __shared__ unsigned chk[4][64];
+  const int c = blockIdx.x, e = blockIdx.z, chunks = gridDim.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int w = blockIdx.y * 256 + 4 * lane;
+  const int r0 = c * HEAD_SHARED_ROWS, r1 = min(r0 + HEAD_SHARED_ROWS, hp.B);
+  const float* h = hp.h + e * hp.sh;
+  const float* d = dout + e * s_dout;
+  float4 acc[HD];
+#pragma unroll
+  for (int o = 0; o < HD; ++o) acc[o] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (w < hp.W) {
+#pragma unroll 8
+    for (int row = r0 + wave; row < r1; row += 4) {
+      const float4 hv = *reinterpret_cast<const float4*>(h + (long long)row * hp.W + w);
+#pragma unroll
+      for (int o = 0; o < HD; ++o) {
+        const float dv = d[(long long)row * HD + o];
+        acc[o].x += hv.x * dv;
+        acc[o].y += hv.y * dv;
+        acc[o].z += hv.z * dv;
+        acc[o].w += hv.w * dv;
+      }
+    }
+  }
+  unsigned own = 0u;
+#pragma unroll
+  for (int o = 0; o < HD; ++o) {
+    red[o][wave][lane] = acc[o];
+    own = digest4(own, acc[o]);
+  }
+  __syncthreads();
+  if (wave == 0 && w < hp.W) {
+    float v[4][HD];
+    unsigned dg[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int o = 0; o < HD; ++o) {
+      const float4 a0 = red[o][0][lane], a1 = red[o][1][lane], a2 = red[o][2][lane], a3 = red[o][3][lane];
+      v[0][o] = a0.x + a1.x + a2.x + a3.x;
+      v[1][o] = a0.y + a1.y + a2.y + a3.y;
+      v[2][o] = a0.z + a1.z + a2.z + a3.z;
+      v[3][o] = a0.w + a1.w + a2.w + a3.w;
+      dg[0] = digest4(dg[0], a0);
+      dg[1] = digest4(dg[1], a1);
+      dg[2] = digest4(dg[2], a2);
+      dg[3] = digest4(dg[3], a3);
+    }
+    float* out = ws_w + (((long long)e * chunks + c) * hp.W + w) * HD;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int o = 0; o < HD; ++o) out[k * HD + o] = v[k][o];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) chk[g][lane] = dg[g];
+  }
+  __syncthreads();
+  if (w < hp.W && chk[wave][lane] != own) head_fault(hp.fault, HEAD_FAULT_WGRAD);
+  if (blockIdx.y == 0) head_shared_bias<HD>(d, r0, r1, ws_b + ((long long)e * chunks + c) * HD);
+}
+
+// any W (the scalar form): 64 columns per block, a column per lane
+template <int HD>
+__global__ __launch_bounds__(256) void head_bwd_weight_shared_scalar_kernel(HeadParams hp,
+                                                                            const float* __restrict__ dout,
+                                                                            long long s_dout, float* __restrict__ ws_w,
+                                                                            float* __restrict__ ws_b) {
+  __shared__ float red[4][64][HD];
+  const int c = blockIdx.x, e = blockIdx.z, chunks = gridDim.x;
+  const int wl = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  const int w = blockIdx.y * 64 + wl;
+  const int r0 = c * HEAD_SHARED_ROWS, r1 = min(r0 + HEAD_SHARED_ROWS, hp.B);
+  const float* h = hp.h + e * hp.sh;
+  const float* d = dout + e * s_dout;
+  float acc[HD];
+#pragma unroll
+  for (int o = 0; o < HD; ++o) acc[o] = 0.f;
+  if (w < hp.W) {
+#pragma unroll 8
+    for (int row = r0 + rg; row < r1; row += 4) {
+      const float hv = h[(long long)row * hp.W + w];
+#pragma unroll
+      for (int o = 0; o < HD; ++o) acc[o] += hv * d[(long long)row * HD + o];
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < HD; ++o) red[rg][wl][o] = acc[o];
+  __syncthreads();
+  if (rg == 0 && w < hp.W) {
+    float* out = ws_w + (((long long)e * chunks + c) * hp.W + w) * HD;
+#pragma unroll
+    for (int o = 0; o < HD; ++o) out[o] = red[0][wl][o] + red[1][wl][o] + red[2][wl][o] + red[3][wl][o];
+  }
+  if (blockIdx.y == 0) head_shared_bias<HD>(d, r0, r1, ws_b + ((long long)e * chunks + c) * HD);
+}
+
+// dWh[e][i] = sum_c ws_w[e][c][i] (i < nw = W hd), dbh[e][o] = sum_c ws_b[e][c][o], c ascending
+__global__ __launch_bounds__(256) void head_shared_finish_kernel(const float* __restrict__ ws_w,
+                                                                 const float* __restrict__ ws_b, int chunks,
+                                                                 long long nw, int hd, float* __restrict__ dWh,
+                                                                 long long sWh, float* __restrict__ dbh,
+                                                                 long long sbh) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const int e = blockIdx.y;
+  if (i >= nw + hd) return;
+  const bool bias = i >= nw;
+  const long long n = bias ? hd : nw, k = bias ? i - nw : i;
+  const float* p = (bias ? ws_b : ws_w) + (long long)e * chunks * n + k;
+  float s = p[0];
+#pragma unroll 4
+  for (int c = 1; c < chunks; ++c) s += p[(long long)c * n];
+  (bias ? dbh + e * sbh : dWh + e * sWh)[k] = s;
+}
+
 // Both halves of a head's backward in ONE launch (they read the same dout and are independent):
 // blocks [0, nd) are head_bwd_data's [W / 256][T_l HB_RS][E] grid, the rest head_bwd_weight's
 // [T_l][W / 256][E] grid -- the same arithmetic per block, one launch fewer per network.
@@ -819,7 +958,7 @@ __global__ __launch_bounds__(256) void head_bwd_fused_kernel(HeadParams hp, cons
   const float* d = dout + e * s_dout;
   float wt[4][HD];
   if (ok) {
-    const float* Wt = hp.Wh + e * hp.sWh + ((long long)t * hp.W + w) * HD;
+    const float* Wt = hp.Wh + e * hp.sWh + ((long long)(hp.shared ? 0 : t) * hp.W + w) * HD;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -1260,6 +1399,7 @@ bool head_backward_both(const HeadParams& hp, const float* dout, long long s_dou
                         const int* rows, int max_rows, int T_l, PlaneOut po, float* dbp, float* dWh, float* dbh,
                         hipStream_t st) {
   if (hp.W % 4 != 0 || !head_kernels_cover(hp.hd, hp.W)) return false;  // the scalar weight kernel: two launches
+  if (hp.shared) return false;  // a shared head's weight grad runs over row chunks (head_backward_weight_shared)
   if (hp.hd > 8) {  // the wide family has no one-launch form: its two kernels, one after the other
     head_backward_data(hp, dout, s_dout, dz, counts, rows, max_rows, T_l, st, po, dbp);
     head_backward_weight_wide(hp, dout, s_dout, counts, rows, max_rows, T_l, dWh, dbh, st);
@@ -1316,6 +1456,41 @@ bool head_backward_weight(const HeadParams& hp, const float* dout, long long s_d
     default: return false;  // (head_kernels_cover)
   }
 #undef HBW_LAUNCH
+  return true;
+}
+
+bool head_backward_weight_shared(const HeadParams& hp, const float* dout, long long s_dout, float* ws, float* dWh,
+                                 float* dbh, hipStream_t st) {
+  if (!head_kernels_cover(hp.hd, hp.W) || hp.B < 1) return false;  // not launched
+  const unsigned chunks = (unsigned)head_shared_chunks(hp.B);
+  const long long nw = (long long)hp.W * hp.hd;
+  float* ws_w = ws;
+  float* ws_b = ws + (long long)hp.E * chunks * nw;
+  const bool vec = hp.W % 4 == 0;
+  if (hp.hd > 8) {
+    const dim3 grid(chunks, (unsigned)((hp.W + 63) / 64), (unsigned)hp.E);
+    WIDE_NT_LAUNCH(wide_nt(hp.hd), head_bwd_weight_shared_wide_kernel, grid, dim3(256), st, hp, dout, s_dout, ws_w, ws_b);
+  } else {
+#define HBS_LAUNCH(HDV)                                                                                             \
+  if (vec)                                                                                                          \
+    hipLaunchKernelGGL(head_bwd_weight_shared_kernel<HDV>, dim3(chunks, (hp.W + 255) / 256, hp.E), dim3(256), 0, st, hp, \
+                       dout, s_dout, ws_w, ws_b);                                                                   \
+  else                                                                                                              \
+    hipLaunchKernelGGL(head_bwd_weight_shared_scalar_kernel<HDV>, dim3(chunks, (hp.W + 63) / 64, hp.E), dim3(256), 0, \
+                       st, hp, dout, s_dout, ws_w, ws_b)
+    switch (hp.hd) {
+      case 1: HBS_LAUNCH(1); break;
+      case 2: HBS_LAUNCH(2); break;
+      case 4: HBS_LAUNCH(4); break;
+      case 6: HBS_LAUNCH(6); break;
+      case 8: HBS_LAUNCH(8); break;
+      default: return false;  // (head_kernels_cover)
+    }
+#undef HBS_LAUNCH
+  }
+  const dim3 fgrid((unsigned)((nw + hp.hd + 255) / 256), (unsigned)hp.E);
+  hipLaunchKernelGGL(head_shared_finish_kernel, fgrid, dim3(256), 0, st, ws_w, ws_b, (int)chunks, nw, hp.hd, dWh, hp.sWh,
+                     dbh, hp.sbh);
   return true;
 }
 

@@ -174,7 +174,8 @@ __device__ inline void policy_wide_tile(const PolicyParams& p, int t, int row_a,
   const HeadParams& hp = p.head;
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   float(*so)[16 * NT + 4] = sp[g];
-  const long long woff = (long long)t * hp.W * hp.hd;
+  const int th = hp.shared ? 0 : t;  // the head's block (a shared head has one)
+  const long long woff = (long long)th * hp.W * hp.hd;
   f32x4 acc[NT];
 #pragma unroll
   for (int c = 0; c < NT; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -189,7 +190,7 @@ __device__ inline void policy_wide_tile(const PolicyParams& p, int t, int row_a,
     if (b < 0) continue;
     const float mu = ((sp[0][r][lj] + sp[1][r][lj]) + sp[2][r][lj]) + sp[3][r][lj];
     const float ls = ((sp[0][r][p.A + lj] + sp[1][r][p.A + lj]) + sp[2][r][p.A + lj]) + sp[3][r][p.A + lj];
-    policy_finish_wide(p, b, t, mu, ls, lane);
+    policy_finish_wide(p, b, th, mu, ls, lane);
   }
 }
 
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void head_bwd_data_wide_kernel(HeadParams hp, 
   const int* rl = rows + (long long)t * max_rows;
   float(*so)[20] = so_all[rs];
   {
-    const float* Wt = hp.Wh + e * hp.sWh + (long long)t * hp.W * hd;
+    const float* Wt = hp.Wh + e * hp.sWh + (long long)(hp.shared ? 0 : t) * hp.W * hd;
     for (int idx = threadIdx.x; idx < 16 * hd4; idx += 256) {
       const int jj = idx / hd4, o = idx - jj * hd4;
       sw[jj][o] = (o < hd && w0 + jj < hp.W) ? Wt[(long long)(w0 + jj) * hd + o] : 0.f;
@@ -360,6 +361,59 @@ __global__ __launch_bounds__(256) void head_bwd_weight_wide_kernel(HeadParams hp
     float s = 0.f;
     for (int jr = 0; jr < n; ++jr) s += d[(long long)rl[jr] * hd + threadIdx.x];
     dbh[e * hp.sbh + t * hd + threadIdx.x] = s;
+  }
+}
+
+// The shared head's form (HeadParams::shared, heads.hip head_bwd_weight_shared_kernel): workgroup (row chunk c,
+// 64 columns, member e), wave g its 16 columns and all outputs.  The chunk's partial ws_w[e][c][w][o] is ONE
+// fmaf chain over the chunk's rows r0, r0 + 1, ... in order (rounded up to 4 with exact zeros); ws_b[e][c][o]:
+// thread o adds the chunk's rows of dout in the same order.  head_shared_finish_kernel adds the chunks.
+template <int NT>
+__global__ __launch_bounds__(256) void head_bwd_weight_shared_wide_kernel(HeadParams hp, const float* __restrict__ dout,
+                                                                           long long s_dout, float* __restrict__ ws_w,
+                                                                           float* __restrict__ ws_b) {
+  const int c0 = blockIdx.x, e = blockIdx.z, chunks = gridDim.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, kk = lane >> 4;
+  const int w0 = blockIdx.y * 64 + 16 * wave, hd = hp.hd;
+  const int r0 = c0 * HEAD_SHARED_ROWS, r1 = min(r0 + HEAD_SHARED_ROWS, hp.B);
+  const float* h = hp.h + e * hp.sh;
+  const float* d = dout + e * s_dout;
+  if (w0 < hp.W) {  // (wave-uniform)
+    f32x4 acc[NT];
+#pragma unroll
+    for (int c = 0; c < NT; ++c) acc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool win = w0 + j < hp.W;
+    for (int k0 = r0; k0 < r1; k0 += 16) {  // four k-steps' loads in flight; they enter the chain in order
+      float a[4], b[4][NT];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int row = k0 + 4 * u + kk;
+        const bool rin = row < r1;
+        a[u] = (rin && win) ? h[(long long)row * hp.W + w0 + j] : 0.f;
+#pragma unroll
+        for (int c = 0; c < NT; ++c) b[u][c] = (rin && 16 * c + j < hd) ? d[(long long)row * hd + 16 * c + j] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (k0 + 4 * u < r1) {  // (uniform)
+#pragma unroll
+          for (int c = 0; c < NT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u][c], acc[c], 0, 0, 0);
+        }
+      }
+    }
+    float* out = ws_w + ((long long)e * chunks + c0) * hp.W * hd;
+#pragma unroll
+    for (int c = 0; c < NT; ++c)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int w = w0 + 4 * kk + v, o = 16 * c + j;
+        if (w < hp.W && o < hd) out[(long long)w * hd + o] = acc[c][v];
+      }
+  }
+  if (blockIdx.y == 0 && (int)threadIdx.x < hd) {
+    float s = 0.f;
+    for (int row = r0; row < r1; ++row) s += d[(long long)row * hd + threadIdx.x];
+    ws_b[((long long)e * chunks + c0) * hd + threadIdx.x] = s;
   }
 }
 

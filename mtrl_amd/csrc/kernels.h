@@ -300,6 +300,9 @@ struct HeadParams {
   long long sWh, sbh, sh;
   unsigned* fault;      // nullable: the head backward's LDS-reduction self-checks OR a bit in here on a
                         // mismatch (HEAD_FAULT_*); the engine reports it at the next sync (check_err)
+  int shared;           // 1: ONE head for all tasks (the Vanilla network's layer_D): Wh [E][W][hd], WhT [hd][W],
+                        // bh [E][hd] -- every row reads task 0's block whatever task[b] says (the forward and
+                        // data-grad kernels; the row lists stay per task)
 };
 // HeadParams::fault bits: which checked cross-wave LDS reduction saw a slot differ from its writer's bits
 constexpr unsigned HEAD_FAULT_WGRAD = 1u;   // the head weight grad's four-wave sum
@@ -416,6 +419,20 @@ void head_backward_weight_inject(const HeadParams& hp, const float* dout, long l
                                  const int* rows, int max_rows, int T_l, float* dWh, float* dbh, hipStream_t st);
 bool head_backward_weight(const HeadParams& hp, const float* dout, long long s_dout, const int* counts,
                           const int* rows, int max_rows, float* dWh, float* dbh, hipStream_t st);
+
+// The shared head's weight and bias grad (HeadParams::shared): dWh[e][w][o] = sum_b h[e][b][w] dout[e][b][o],
+// dbh[e][o] = sum_b dout[e][b][o] over ALL B rows (no row lists).  Two launches: the rows in chunks of
+// HEAD_SHARED_ROWS, grid [chunks][W tiles][E], each workgroup's partial sums to ws ([E][chunks][W hd] then
+// [E][chunks][hd]: head_shared_ws_floats), then a finish pass that adds the chunks in ascending order.  No
+// atomics: the sums have one order, fixed by (B, W, hd).  W % 4 == 0: 16-B loads, the four-wave LDS sum
+// self-checked (HEAD_FAULT_WGRAD); other W: the scalar form (hd <= 8 only, as head_kernels_cover).
+constexpr int HEAD_SHARED_ROWS = 64;
+inline int head_shared_chunks(int B) { return (B + HEAD_SHARED_ROWS - 1) / HEAD_SHARED_ROWS; }
+inline long long head_shared_ws_floats(int B, int W, int hd, int E) {
+  return (long long)E * head_shared_chunks(B) * ((long long)W * hd + hd);
+}
+bool head_backward_weight_shared(const HeadParams& hp, const float* dout, long long s_dout, float* ws, float* dWh,
+                                 float* dbh, hipStream_t st);
 
 // critic data grad into the action columns + tanh-normal backward -> actor head grad
 struct ActionGradParams {
@@ -625,9 +642,11 @@ void task_select(const float* G, int T, long long P, const long long* ranks, flo
 void task_pair_stats(const float* G, int T, long long P, const float* thr, float eps, float tau, int grid,
                      double* ws_gram_part, double* ws_l1_part, unsigned long long* counts, unsigned long long* nz,
                      double* gram, double* l1, hipStream_t st);
-// dst[t*P + dst_off + e*dst_ms + t*blk + i] = src[src_off + e*src_ms + t*blk + i], i < blk (per-task head blocks)
+// dst[t*P + dst_off + e*dst_ms + t*blk + i] = src[src_off + e*src_ms + t*blk + i], i < blk (per-task head blocks);
+// tied (a head shared by the tasks): dst[t*P + dst_off + e*dst_ms + i] instead -- row t's gradient of the one head
 void scatter_task_blocks(const float* src, long long src_off, long long src_ms, float* dst, long long P,
-                         long long dst_off, long long dst_ms, int E, int T, long long blk, hipStream_t st);
+                         long long dst_off, long long dst_ms, int E, int T, long long blk, hipStream_t st,
+                         bool tied = false);
 // *err |= 1 unless task[r] == r % T_l for every row (rows interleaved i*T + t, as the buffer samples)
 void check_interleaved(const int* task, int B, int T_l, int* err, hipStream_t st);
 

@@ -58,12 +58,16 @@ def make_config(**kw) -> Config:
 class MTSACEngine:
     """One engine per GPU: device-resident replay buffer + MTSAC update."""
 
-    def __init__(self, config: Config, device: int = 0):
+    def __init__(self, config: Config, device: int = 0, shared_head: bool = False):
+        """shared_head: the reference's VanillaNetwork (MTSAC_NET_SHARED_HEAD): one head layer_D for all tasks,
+        parameter vectors in that tree's leaf order (layer_0 .. layer_D, the head last; mtrl_amd.init)."""
         self.lib = _lib.load()
         self.config = config
         self.device = device
+        self.shared_head = bool(shared_head)
         h = ctypes.c_void_p()
-        check(self.lib.mtsac_create(ctypes.byref(config), device, ctypes.byref(h)))
+        flags = _lib.NET_SHARED_HEAD if shared_head else 0
+        check(self.lib.mtsac_create_flags(ctypes.byref(config), flags, device, ctypes.byref(h)))
         self._h = h
         c = config
         self.T_l = c.task_count

@@ -43,6 +43,32 @@ def init_flat(rng: np.random.Generator, shapes, head_bound: float) -> dict[str, 
     return out
 
 
+def vanilla_leaf_shapes(in_dim: int, width: int, depth: int, head_dim: int, ens: int | None):
+    """Leaves of the reference's VanillaNetwork -> MLP (mtrl/nn/base.py:11-89) in flax leaf order: ``depth``
+    Dense+ReLU layers layer_0 .. layer_{D-1} then the Dense head layer_D, which every task shares, each as
+    bias then kernel.  The head keeps the names head_b / head_W (init_flat draws them as heads); it comes LAST:
+    the order of ``mtsac_set_params`` on a shared-head engine."""
+    pre = () if ens is None else (ens,)
+    shapes, fan = [], in_dim
+    for i in range(depth):
+        shapes.append((f"b{i}", pre + (width,)))
+        shapes.append((f"W{i}", pre + (fan, width)))
+        fan = width
+    return shapes + [("head_b", pre + (head_dim,)), ("head_W", pre + (width, head_dim))]
+
+
+def init_vanilla(num_tasks: int, obs_dim: int, action_dim: int, actor_width: int, actor_depth: int, critic_width: int,
+                 critic_depth: int, num_critics: int, seed: int = 1):
+    """(actor_flat, critic_flat) of the shared-head (Vanilla) networks: trunk he_uniform with zero biases, head
+    kernel and bias uniform(1e-3) for the actor and uniform(3e-3) for the critic (networks.py:33-34, 65-66:
+    ``head_bias_init or bias_init`` with base.py:57-58).  num_tasks only documents the one-hot inside obs_dim."""
+    del num_tasks
+    rng = np.random.default_rng(seed)
+    ash = vanilla_leaf_shapes(obs_dim, actor_width, actor_depth, 2 * action_dim, None)
+    csh = vanilla_leaf_shapes(action_dim + obs_dim, critic_width, critic_depth, 1, num_critics)
+    return flatten(init_flat(rng, ash, 1e-3), ash), flatten(init_flat(rng, csh, 3e-3), csh)
+
+
 def slice_tasks(p: dict[str, np.ndarray], begin: int, count: int, ens: bool) -> dict[str, np.ndarray]:
     """Keep the heads of tasks [begin, begin+count) (task sharding)."""
     q = dict(p)

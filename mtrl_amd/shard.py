@@ -17,10 +17,16 @@ import numpy as np
 from . import _lib
 
 
-def shard_tasks(num_tasks: int, world: int, rank: int) -> tuple[int, int]:
-    """Contiguous split: MT50 over 8 ranks -> 7,7,6,6,6,6,6,6."""
+def shard_tasks(num_tasks: int, world: int, rank: int, shared_head: bool = False) -> tuple[int, int]:
+    """Contiguous split: MT50 over 8 ranks -> 7,7,6,6,6,6,6,6.
+
+    shared_head: the split is for shared-head (Vanilla) engines, which cannot be task-sharded -- the head's
+    gradient is in no collective; raises as ``mtsac_create_flags`` does (-95) for world > 1."""
     if not 0 <= rank < world or world > num_tasks:
         raise ValueError("need 0 <= rank < world <= num_tasks")
+    if shared_head and world > 1:
+        raise _lib.MTSACError("libmtsac error -95: a shared head on a task-sharded engine is not supported: its "
+                              "gradient would have to join the trunk's all-reduce buckets and the sharded optimizer")
     base, rem = divmod(num_tasks, world)
     begin = rank * base + min(rank, rem)
     return begin, base + (1 if rank < rem else 0)
