@@ -63,7 +63,43 @@ constexpr int PART = 1024;       // max partial-sum blocks
 
 long long align_up(long long x, long long a) { return (x + a - 1) / a * a; }
 
+// precision split2h: a device record (kernels.h PlaneRec: exponent + partial maxima) per fp16 plane
+// tensor; n = the partial maxima its last producer wrote (0: consumers bound it by 2^(15 - e))
+struct RecRef {
+  PlaneRec* d = nullptr;
+  int n = 0;
+};
+
+// ---- the operands of a trunk pass: an input, an activation set and (backward) a data-grad set, each built
+// once at create over buffers that belong together.  Plain views: buffers and records live in the engine.
+// The input: fp32 rows, and their planes [3][arows][xld] under the split2h record they were written with
+struct TrunkIn {
+  const float* x = nullptr;
+  int ld = 0;
+  __bf16* p = nullptr;  // null: no planes (fp32, the rollout)
+  RecRef* rec = nullptr;
+};
+// Per-layer tensors of one network: the activations of a forward (planes of layers 0..D-2) or the
+// pre-activation grads of a backward (planes of layers 1..D-1, and 0 for the plane input weight grad)
+template <int Kind>
+struct LayerSet {
+  float** f = nullptr;    // [depth] fp32
+  __bf16** p = nullptr;   // [depth] planes; null: the pass runs on fp32 operands
+  RecRef* rec = nullptr;  // [depth] the planes' records
+  LayerSet f32() const { return LayerSet{f, nullptr, nullptr}; }
+};
+using ActSet = LayerSet<0>;
+using GradSet = LayerSet<1>;
+
+enum { NET_ACTOR = 0, NET_CRITIC = 1 };
+
 struct Net {
+  // which network (its slot in zstep, r_w, wparts, wgrid, wbh: [actor, critic]), its Adam learning rate,
+  // the record of its head backward's input (critic dq, actor dout); set at create
+  int id = NET_ACTOR;
+  float lr = 0.f;
+  RecRef* r_dhead = nullptr;
+  void bind(int id_, float lr_, RecRef* r) { id = id_, lr = lr_, r_dhead = r; }
   int in_dim = 0, in_ld = 0, width = 0, depth = 0, T_l = 0, hd = 0, E = 1;
   // shared: ONE head for all tasks (the Vanilla network's layer_D, MTSAC_NET_SHARED_HEAD).  The device layout
   // keeps the head region in front of trunk_off with Th = 1 head block instead of T_l, so the clip norm, the
@@ -208,13 +244,16 @@ struct mtsac_engine {
   // still reads -- the actor input rows (its layer-0 weight grad) and the task row lists (actor
   // heads, temperature) -- alternates between two sets; everything else the early segments write
   // is dead by the time step k's actor-loss pass (s_ap) has run, which they wait for.
+  // A step's trunk inputs are its set's, all under the set's one record r_in[k]: a (xa) and an (its s' rows)
+  // with the set's own planes (the weight grad reads them after s_ap); c, cn, cp (xc, xcn, xcp) are shared.
   struct InSet {
     float* xa;
-    __bf16* xap;  // planes of xa (the input-layer GEMMs' operand; the weight grad reads them after s_ap)
     int *task, *counts, *rows;
+    TrunkIn a, an, c, cn, cp;
   };
   InSet inset[2] = {};
   int inset_cur = 0;
+  const InSet& in() const { return inset[inset_cur]; }
   // Device-sampled batches are interleaved (row i*T_l + t, buffers.py:548), so their per-task row
   // lists are fixed: counts = n, rows[t][i] = i*T_l + t, uploaded once (no task_rows launch per step)
   int *s_counts = nullptr, *s_rows = nullptr;
@@ -266,13 +305,8 @@ struct mtsac_engine {
   // either form (set at create)
   bool in_wgrad_planes = false;
   int np = 3;  // operand planes the plane GEMMs read: 3 (split3), 1 (bf16) or 2 (split2h: fp16)
-  // ---- precision split2h: a device record (kernels.h PlaneRec: exponent + partial maxima) per fp16
-  // plane tensor; n = the partial maxima its last producer wrote (0: consumers bound it by 2^(15 - e))
+  // ---- precision split2h: the plane tensors' records (RecRef)
   bool h2 = false;
-  struct RecRef {
-    PlaneRec* d = nullptr;
-    int n = 0;
-  };
   PlaneRec* recs = nullptr;
   RecRef r_in[2];         // the step's input planes (xa / xc / xc_next / xc_pi), per input set
   RecRef r_w[2][2];       // weights [0 actor, 1 critic][0 params, 1 Polyak target]
@@ -284,11 +318,7 @@ struct mtsac_engine {
   float* wparts[2] = {};    // the optimizer's per-block max |p_new| [actor, critic] and the target's
   float* tparts = nullptr;
   int wgrid[2] = {}, wbh[2] = {};  // the last optimizer launch's grid and head blocks per network
-  RecRef* act_rec(__bf16** actp) {
-    return actp == hap || actp == hap_s2 ? r_ac[0] : actp == hcp ? r_ac[1] : actp == hctp ? r_ac[2] : nullptr;
-  }
-  RecRef* dz_rec(__bf16** dzp) { return dzp == dzap ? r_dz[0] : dzp == dzcp ? r_dz[1] : nullptr; }
-  RecRef& w_rec(const Net& net, int which) { return r_w[&net == &critic ? 1 : 0][which]; }
+  RecRef& w_rec(const Net& net, int which) { return r_w[net.id][which]; }
   // |one Adam step| / lr: by Cauchy-Schwarz |m_t| <= (1 - b1) / sqrt((1 - b2)(1 - b1^2 / b2)) sqrt(v_t) for
   // any gradient sequence, times the bias corrections' ratio sqrt(1 - b2^t) / (1 - b1^t) at its worst
   // step t (<= 1 at b1 = 0.9, b2 = 0.999: 7.27 in all); 25 % margin.  Computed once at create.
@@ -321,19 +351,16 @@ struct mtsac_engine {
   __bf16* hctp[MAXD] = {};
   __bf16* dzap[MAXD] = {};
   __bf16* dzcp[MAXD] = {};
+  // the passes' operand sets over these arrays: the actor over [s | s'], its s' view (one tensor: the actor's
+  // records), the critic, the target critic; the backward passes' grads.  fp32-operand passes take .f32().
+  const ActSet acts_a{ha, hap, r_ac[0]}, acts_an{han, hap_s2, r_ac[0]}, acts_c{hc, hcp, r_ac[1]},
+      acts_ct{hct, hctp, r_ac[2]};
+  const GradSet grads_a{dza, dzap, r_dz[0]}, grads_c{dzc, dzcp, r_dz[1]};
+  const ActSet& acts_of(const Net& net) const { return net.id == NET_ACTOR ? acts_a : acts_c; }
+  const GradSet& grads_of(const Net& net) const { return net.id == NET_ACTOR ? grads_a : grads_c; }
+  const TrunkIn& in_of(const Net& net) const { return net.id == NET_ACTOR ? in().a : in().c; }
+  int fwd_rows(const Net& net) const { return net.id == NET_ACTOR ? Ma : B; }  // the step's widest forward
   float* cs_part = nullptr;  // column-sum partials (bias grads beside the plane weight-grad GEMM)
-  // planes of the GEMM-ready trunk inputs (xa, xan, xc, xcn, xcp): [3][arows][xld]
-  struct InPlanes {
-    const float* x;
-    __bf16* p;
-  };
-  InPlanes inp[5] = {};
-  __bf16* in_planes(const float* X) const {
-    for (const InPlanes& q : inp)
-      if (q.x == X) return q.p;
-    if (X == xan && inp[0].p) return inp[0].p + actor.krows * actor.xld;  // the s' rows of xa's planes
-    return nullptr;
-  }
   // Split actor forward (device collective, eager one stream): the s' rows (a' for the TD target) run
   // before the critic loss as always, the s rows (pi(s) for the actor loss) beside the critic's trunk
   // all-reduce -- the one stretch of the step where nothing else may run (the rest needs the updated
@@ -378,14 +405,11 @@ struct mtsac_engine {
   // rows, the data grad with and without the bias grad's column sums.  Called at create once the
   // workspaces and the activation / plane buffers exist.
   bool frag_probe(Net& net, int li) {
-    const bool is_actor = &net == &actor;
-    float **acts = is_actor ? ha : hc, **dz = is_actor ? dza : dzc;
-    __bf16 **actp = is_actor ? hap : hcp, **dzp = is_actor ? dzap : dzcp;
-    __bf16* xp = in_planes(is_actor ? xa : xc);
-    for (int M : {B, is_actor ? Ma : B})
-      if (!gemm_x3f_ok(fwd_params(net, net.p, 0, xp, acts, actp, li, M), EPI_BIAS_RELU, net.E)) return false;
+    for (int M : {B, fwd_rows(net)})
+      if (!gemm_x3f_ok(fwd_params(net, net.p, 0, in_of(net), acts_of(net), li, M), EPI_BIAS_RELU, net.E)) return false;
     for (int want_db = 0; want_db < 2 && li > 0; ++want_db)
-      if (!gemm_x3f_ok(dgrad_params(net, acts, actp, dz, dzp, li, B, want_db != 0), EPI_RELU_MASK, net.E)) return false;
+      if (!gemm_x3f_ok(dgrad_params(net, acts_of(net), grads_of(net), li, B, want_db != 0), EPI_RELU_MASK, net.E))
+        return false;
     return true;
   }
   float* pn = nullptr;  // [critic trunk |p|^2, actor trunk, critic heads, actor heads]
@@ -401,6 +425,8 @@ struct mtsac_engine {
   float *r_obs = nullptr, *r_x = nullptr, *r_eps = nullptr, *r_act = nullptr, *r_lp = nullptr, *r_dummy = nullptr;
   float* r_h[MAXD] = {};
   int* r_task = nullptr;
+  TrunkIn in_r;                                  // r_x: fp32 rows only
+  const ActSet acts_r{r_h, nullptr, nullptr};  // fp32 only
   // graph
   bool use_graph = true;
   hipGraph_t graph = nullptr;
@@ -690,22 +716,21 @@ struct mtsac_engine {
 
   // planes of the top layer's data grad (written by the head backward), when the trunk has
   // hidden layers that read them
-  PlaneOut top_planes(Net& net, __bf16** dzp) {
+  PlaneOut top_planes(Net& net, const GradSet& dz) {
     PlaneOut po{};
-    if (planes && net.depth > 1) {
-      po.p = dzp[net.depth - 1];
+    if (planes && net.depth > 1 && dz.p) {
+      po.p = dz.p[net.depth - 1];
       po.ld = net.ald;
       po.ps = net.aps();
       po.sm = 3 * net.aps();
       if (h2) {  // bound: hd * max|dout| * (max|head weight| + one Adam step)
-        RecRef& top = dz_rec(dzp)[net.depth - 1];
-        RecRef& d = &net == &critic ? r_dq : r_dout;
+        RecRef& top = dz.rec[net.depth - 1];
         po.rc = top.d;
         top.n = 0;  // no partial maxima: the planes' range bounds dz_top for the next producer
-        po.rd = d.d;
-        po.nd = d.n;
+        po.rd = net.r_dhead->d;
+        po.nd = net.r_dhead->n;
         po.rw = w_rec(net, 0).d;
-        po.w_add = adam_step_bound() * (&net == &critic ? cfg.critic_lr : cfg.actor_lr);
+        po.w_add = adam_step_bound() * net.lr;
         po.kmul = (float)net.hd;
       }
     }
@@ -714,16 +739,16 @@ struct mtsac_engine {
 
   // head backward into the top layer's data grad.  With planes the GEMMs read only the planes: the
   // fp32 dz is skipped and (want_db) the bias grad's column sums come out of the same pass.
-  void head_bwd(Net& net, const HeadParams& hp, const float* dout, long long s_dout, float** dz, __bf16** dzp,
-                bool want_db, const int* slot = nullptr) {
+  void head_bwd(Net& net, const HeadParams& hp, const float* dout, long long s_dout, const GradSet& dz, bool want_db,
+                const int* slot = nullptr) {
     const int top = net.depth - 1;
-    const PlaneOut po = top_planes(net, dzp);
+    const PlaneOut po = top_planes(net, dz);
     if (slot != nullptr) {  // compacted (actor_compact's conditions: planes, no bias grad)
       head_backward_data(hp, dout, s_dout, nullptr, counts, rows, B, T_l, cur, po, nullptr, slot);
       return;
     }
     if (po.p == nullptr) {
-      head_backward_data(hp, dout, s_dout, dz[top], counts, rows, B, T_l, cur, po);
+      head_backward_data(hp, dout, s_dout, dz.f[top], counts, rows, B, T_l, cur, po);
       net.dbp_chunks[top] = 0;
       return;
     }
@@ -733,9 +758,10 @@ struct mtsac_engine {
 
   // head_bwd plus the head's weight/bias grad (head_backward_weight) in ONE launch; false: not
   // launched (fp32 dz without planes, or W % 4 != 0), the caller issues the two passes
-  bool head_bwd_both(Net& net, const HeadParams& hp, const float* dout, long long s_dout, __bf16** dzp, bool want_db) {
+  bool head_bwd_both(Net& net, const HeadParams& hp, const float* dout, long long s_dout, const GradSet& dz,
+                     bool want_db) {
     const int top = net.depth - 1;
-    const PlaneOut po = top_planes(net, dzp);
+    const PlaneOut po = top_planes(net, dz);
     if (po.p == nullptr) return false;
     float* dbp = want_db ? net.dbp[top] : nullptr;
     if (!head_backward_both(hp, dout, s_dout, nullptr, counts, rows, B, T_l, po, dbp, net.g + net.off_hW,
@@ -751,16 +777,16 @@ struct mtsac_engine {
   // operands, shape and outputs from these three; the step adds only the split2h records (h2_gemm).
   // The sizing runs before the buffers exist: it reads the shape fields, the pointers are null then.
 
-  // Forward of layer i over M rows (EPI_BIAS_RELU): in_i . W_i + b_i, in_i = xp (the input's planes) or
-  // actp[i - 1]; which 0 / 1: params is Net::p / Net::tgt.  net.x3f: both operands row-major, against the
+  // Forward of layer i over M rows (EPI_BIAS_RELU): in_i . W_i + b_i, in_i = in.p (the input's planes) or
+  // a.p[i - 1]; which 0 / 1: params is Net::p / Net::tgt.  net.x3f: both operands row-major, against the
   // W_i^T planes (gemm_x3f / gemm_x3s), and hidden activations keep planes only; else against W_i's
   // k-major planes (gemm_x3p), fp32 output at every layer.
-  SplitGemmParams fwd_params(Net& net, const float* params, int which, const __bf16* xp, float** acts, __bf16** actp,
-                             int i, int M) {
+  SplitGemmParams fwd_params(Net& net, const float* params, int which, const TrunkIn& in, const ActSet& a, int i,
+                             int M) {
     const bool last = i == net.depth - 1;
     SplitGemmParams g{};
     g.np = np;
-    g.A = i == 0 ? xp : actp[i - 1];
+    g.A = i == 0 ? in.p : a.p[i - 1];
     g.lda = i == 0 ? net.xld : net.ald;
     g.pA = i == 0 ? net.arows * net.xld : net.aps();
     g.sA = i == 0 ? 0 : 3 * net.aps();  // the input is shared by the ensemble members
@@ -778,12 +804,12 @@ struct mtsac_engine {
       g.b_kmajor = 1;
     }
     if (last || !net.x3f) {  // the heads read fp32
-      g.C = acts[i];
+      g.C = a.f[i];
       g.ldc = net.width;
       g.sC = (long long)M * net.width;
     }
     if (!last) {  // the next layer reads the planes (x3f: so does the data grad's ReLU mask)
-      g.Cp = actp[i];
+      g.Cp = a.p[i];
       g.ldcp = net.ald;
       g.pC = net.aps();
       g.sCp = 3 * net.aps();
@@ -809,11 +835,11 @@ struct mtsac_engine {
   // only then) is the number of row chunks it leaves, 0 when neither kernel takes that form.
   // ragged: the launch over the members' active rows (gemm_x3f_ragged: dz[i]'s planes are compacted,
   // so are the outputs); needs split2h, net.x3f, no want_db, and gemm_x3f_ragged_ok of the result.
-  SplitGemmParams dgrad_params(Net& net, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i, int M,
-                               bool want_db, bool ragged = false, int* db_chunks = nullptr) {
+  SplitGemmParams dgrad_params(Net& net, const ActSet& a, const GradSet& dz, int i, int M, bool want_db,
+                               bool ragged = false, int* db_chunks = nullptr) {
     SplitGemmParams g{};
     g.np = np;
-    g.A = dzp[i];
+    g.A = dz.p[i];
     g.lda = net.ald;
     g.pA = net.aps();
     g.sA = 3 * net.aps();
@@ -822,21 +848,21 @@ struct mtsac_engine {
     g.pB = net.wps();
     g.sB = 3 * net.wps();
     g.b_frag = net.bfrag[i] ? 1 : 0;
-    g.C = dz[i - 1];
+    g.C = dz.f[i - 1];
     g.ldc = net.width;
     g.sC = (long long)M * net.width;
     if (net.x3f) {  // hidden activations keep planes only: h > 0 <=> its bf16 high plane > 0
-      g.mask16 = actp[i - 1];
+      g.mask16 = a.p[i - 1];
       g.ldm = (int)net.ald;
       g.sMask = 3 * net.aps();
     } else {
-      g.mask = acts[i - 1];
+      g.mask = a.f[i - 1];
       g.ldm = net.width;
       g.sMask = (long long)M * net.width;
     }
     g.pMask = net.aps();
-    if (dzp[i - 1] && (i - 1 >= 1 || want_db)) {  // dz[0]'s planes feed only its weight grad
-      g.Cp = dzp[i - 1];
+    if (dz.p[i - 1] && (i - 1 >= 1 || want_db)) {  // dz[0]'s planes feed only its weight grad
+      g.Cp = dz.p[i - 1];
       g.ldcp = net.ald;
       g.pC = net.aps();
       g.sCp = 3 * net.aps();
@@ -872,15 +898,15 @@ struct mtsac_engine {
   // bias grad) is deferred to the network's optimizer and the slabs wait in ws_wg[i] (null: this weight
   // grad never splits).  Where dz[i]'s producer left column sums (dbp_chunks[i] > 0) the GEMM's finish
   // makes the bias grad from them (cs_part set); else the caller runs colsum on the fp32 dz[i].
-  SplitGemmParams wgrad_params(Net& net, const __bf16* xp, __bf16** actp, __bf16** dzp, int i) {
+  SplitGemmParams wgrad_params(Net& net, const TrunkIn& in, const ActSet& a, const GradSet& dz, int i) {
     SplitGemmParams g{};
     g.np = np;
-    g.A = i == 0 ? xp : actp[i - 1];
+    g.A = i == 0 ? in.p : a.p[i - 1];
     g.lda = i == 0 ? net.xld : net.ald;
     g.pA = i == 0 ? net.arows * net.xld : net.aps();
     g.sA = i == 0 ? 0 : 3 * net.aps();
     g.a_kmajor = 1;
-    g.B = dzp[i];
+    g.B = dz.p[i];
     g.ldb = net.ald;
     g.pB = net.aps();
     g.sB = 3 * net.aps();
@@ -912,35 +938,31 @@ struct mtsac_engine {
   // ------------------------------------------------------------ trunk passes
   // acts[i] = relu(in_i @ W_i + b_i) for every member (batched over the ensemble)
   // which: 0 / 1 = params is Net::p / Net::tgt (their transposed copies or planes are current),
-  // -1 = plain NN form.  actp (split3): planes of acts[0..D-2] to produce, or null.
-  void trunk_forward(Net& net, const float* params, int which, const float* X, int ldx, float** acts, __bf16** actp,
-                     int M) {
-    const bool pl = planes && which >= 0 && actp != nullptr;
+  // -1 = plain NN form.  a.p: planes of a.f[0..D-2] to produce, or null (fp32 operands: in.p is not read).
+  void trunk_forward(Net& net, const float* params, int which, const TrunkIn& in, const ActSet& a, int M) {
+    const bool pl = planes && which >= 0 && a.p != nullptr;
     // the input's planes were written with its fp32 rows: the gather (observations, logged
     // actions) and the policy head (the a' / a columns of xc_next / xc_pi); rows >= M and columns
     // >= in_dim stay zero
-    __bf16* xp = pl ? in_planes(X) : nullptr;
     for (int i = 0; i < net.depth; ++i) {
       const bool last = i == net.depth - 1;
-      if (pl && (i > 0 || xp)) {  // on planes
-        SplitGemmParams g = fwd_params(net, params, which, xp, acts, actp, i, M);
-        if (h2) {
-          RecRef* ar = act_rec(actp);
-          h2_gemm(g, i == 0 ? &r_in[inset_cur] : &ar[i - 1], &w_rec(net, which), last ? nullptr : &ar[i],
+      if (pl && (i > 0 || in.p)) {  // on planes
+        SplitGemmParams g = fwd_params(net, params, which, in, a, i, M);
+        if (h2)
+          h2_gemm(g, i == 0 ? in.rec : &a.rec[i - 1], &w_rec(net, which), last ? nullptr : &a.rec[i],
                   (float)(i == 0 ? net.in_dim : net.width), true);
-        }
         gemmp(g, EPI_BIAS_RELU, net.E, i == 0 ? MTSAC_FAM_INPUT_FORWARD : MTSAC_FAM_FORWARD);
         continue;
       }
       GemmParams g{};
-      g.A = (i == 0) ? X : acts[i - 1];
-      g.lda = (i == 0) ? ldx : net.width;
+      g.A = (i == 0) ? in.x : a.f[i - 1];
+      g.lda = (i == 0) ? in.ld : net.width;
       g.sA = (i == 0) ? 0 : (long long)M * net.width;
       const bool nt = !planes && which >= 0 && i > 0;
       g.B = nt ? net.wt[which][i] : params + net.off_W[i];
       g.ldb = net.width;
       g.sB = net.ms_W[i];
-      g.C = acts[i];
+      g.C = a.f[i];
       g.ldc = net.width;
       g.sC = (long long)M * net.width;
       g.bias = params + net.off_b[i];
@@ -949,7 +971,7 @@ struct mtsac_engine {
       g.N = net.width;
       g.K = (i == 0) ? net.in_dim : net.width;
       if (pl && !last) {
-        g.Cp = actp[i];
+        g.Cp = a.p[i];
         g.ldcp = net.ald;
         g.pC = net.aps();
         g.sCp = 3 * net.aps();
@@ -1015,27 +1037,25 @@ struct mtsac_engine {
   // Backward through trunk layer i, split so the two halves can run concurrently:
   //   wgrad_layer: dW_i = in_i^T dz[i] (+ db_i fused into the GEMM's m-tile-0 blocks)
   //   dgrad_layer: dz[i-1] = (dz[i] W_i^T) * [acts[i-1] > 0]
-  void wgrad_layer(Net& net, const float* X, int ldx, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
-                   int M) {
-    const __bf16* xp = (planes && i == 0) ? in_planes(X) : nullptr;
+  void wgrad_layer(Net& net, const TrunkIn& in, const ActSet& a, const GradSet& dz, int i, int M) {
     // the top layer's dz planes exist only where the head backward writes them (top_planes: a trunk with
     // hidden layers); a one-layer trunk's head backward leaves the fp32 dz[0], which the fp32-operand GEMM
-    // below reads (its dzp[0] buffer is never written: the plane GEMM on it gave dW_0 = 0)
-    const bool dz_planes = i + 1 < net.depth || top_planes_ptr(net, dzp) != nullptr;
-    if (planes && dz_planes && (i > 0 || xp) && actp && dzp && dzp[i]) {  // TN on k-major planes; bias grad by column sums
-      SplitGemmParams g = wgrad_params(net, xp, actp, dzp, i);
-      if (h2) h2_gemm(g, i == 0 ? &r_in[inset_cur] : &act_rec(actp)[i - 1], &dz_rec(dzp)[i], nullptr, (float)g.K, false);
+    // below reads (its dz.p[0] buffer is never written: the plane GEMM on it gave dW_0 = 0)
+    const bool dz_planes = i + 1 < net.depth || top_planes_ptr(net, dz) != nullptr;
+    if (planes && dz_planes && (i > 0 || in.p) && a.p && dz.p && dz.p[i]) {  // TN on k-major planes; bias grad by column sums
+      SplitGemmParams g = wgrad_params(net, in, a, dz, i);
+      if (h2) h2_gemm(g, i == 0 ? in.rec : &a.rec[i - 1], &dz.rec[i], nullptr, (float)g.K, false);
       gemmp(g, EPI_STORE, net.E, i == 0 ? MTSAC_FAM_INPUT_WEIGHT_GRAD : MTSAC_FAM_WEIGHT_GRAD);
       if (net.dbp_chunks[i] <= 0)  // no column sums came with dz[i]
-        colsum(dz[i], M, net.width, net.width, (long long)M * net.width, net.E, cs_part, net.g + net.off_b[i],
+        colsum(dz.f[i], M, net.width, net.width, (long long)M * net.width, net.E, cs_part, net.g + net.off_b[i],
                net.ms_b, cur);
       return;
     }
     GemmParams g{};
-    g.A = (i == 0) ? X : acts[i - 1];  // [K=rows][M=fan_in] storage -> TA
-    g.lda = (i == 0) ? ldx : net.width;
+    g.A = (i == 0) ? in.x : a.f[i - 1];  // [K=rows][M=fan_in] storage -> TA
+    g.lda = (i == 0) ? in.ld : net.width;
     g.sA = (i == 0) ? 0 : (long long)M * net.width;
-    g.B = dz[i];
+    g.B = dz.f[i];
     g.ldb = net.width;
     g.sB = (long long)M * net.width;
     g.C = net.g + net.off_W[i];
@@ -1052,11 +1072,11 @@ struct mtsac_engine {
   }
 
   // want_db, ragged: see dgrad_params (ragged only where actor_compact holds)
-  void dgrad_layer(Net& net, const float* params, float** acts, __bf16** actp, float** dz, __bf16** dzp, int i,
-                   int M, bool want_db = true, bool ragged = false) {
-    if (planes && dzp) {
-      SplitGemmParams g = dgrad_params(net, acts, actp, dz, dzp, i, M, want_db, ragged, &net.dbp_chunks[i - 1]);
-      if (h2) h2_gemm(g, &dz_rec(dzp)[i], &w_rec(net, 0), g.Cp ? &dz_rec(dzp)[i - 1] : nullptr, (float)net.width, false);
+  void dgrad_layer(Net& net, const float* params, const ActSet& a, const GradSet& dz, int i, int M,
+                   bool want_db = true, bool ragged = false) {
+    if (planes && dz.p) {
+      SplitGemmParams g = dgrad_params(net, a, dz, i, M, want_db, ragged, &net.dbp_chunks[i - 1]);
+      if (h2) h2_gemm(g, &dz.rec[i], &w_rec(net, 0), g.Cp ? &dz.rec[i - 1] : nullptr, (float)net.width, false);
       if (ragged) {
         // the members' active rows add up to M (more only on exact ties): M rows of products, not E M
         t_begin(MTSAC_FAM_DATA_GRAD, g.M, g.N, g.K, 1);
@@ -1070,16 +1090,16 @@ struct mtsac_engine {
       return;
     }
     GemmParams g{};
-    g.A = dz[i];
+    g.A = dz.f[i];
     g.lda = net.width;
     g.sA = (long long)M * net.width;
     g.B = params + net.off_W[i];  // W_i (fan_in x W) == [N=fan_in][K=W]
     g.ldb = net.width;
     g.sB = net.ms_W[i];
-    g.C = dz[i - 1];
+    g.C = dz.f[i - 1];
     g.ldc = net.width;
     g.sC = (long long)M * net.width;
-    g.mask = acts[i - 1];
+    g.mask = a.f[i - 1];
     g.ldm = net.width;
     g.sMask = (long long)M * net.width;
     g.M = M;
@@ -1093,14 +1113,16 @@ struct mtsac_engine {
   // gemm_x3s / gemm_x3p shapes and the other precisions keep the dense pass)
   bool actor_compact(int M) {
     if (actor_dense || !h2 || !planes || !critic.x3f || critic.E != 2 || critic.hd != 1 || critic.depth < 2 ||
-        critic.width % 4 != 0 || top_planes_ptr(critic, dzcp) == nullptr)
+        critic.width % 4 != 0 || top_planes_ptr(critic, grads_c) == nullptr)
       return false;
     for (int i = critic.depth - 1; i > 0; --i)
-      if (!gemm_x3f_ragged_ok(dgrad_params(critic, hc, hcp, dzc, dzcp, i, M, false, true), EPI_RELU_MASK, critic.E))
+      if (!gemm_x3f_ragged_ok(dgrad_params(critic, acts_c, grads_c, i, M, false, true), EPI_RELU_MASK, critic.E))
         return false;
     return true;
   }
-  __bf16* top_planes_ptr(Net& net, __bf16** dzp) const { return planes && net.depth > 1 ? dzp[net.depth - 1] : nullptr; }
+  __bf16* top_planes_ptr(const Net& net, const GradSet& dz) const {
+    return planes && net.depth > 1 && dz.p ? dz.p[net.depth - 1] : nullptr;
+  }
 
   HeadParams head(Net& net, const float* params, const float* h, int M, const int* tsk) {
     HeadParams hp{};
@@ -1201,7 +1223,7 @@ struct mtsac_engine {
       if ((e[i] - b[i]) % (4LL * W) != 0) return false;
     return true;
   }
-  bool zero_of(const Net& net) const { return zstep[&net == &critic ? 1 : 0]; }
+  bool zero_of(const Net& net) const { return zstep[net.id]; }
 
   // clip + Adam (+ Polyak) over one network; gradient already complete (and reduced).  Two launches
   // (optim.hip sumsq2 + adam_fused): the |g|^2 partials (and the Adam count), then one update pass
@@ -1244,8 +1266,8 @@ struct mtsac_engine {
     adam_fused(a, at, tp, f, cur);
     net.n_pph = f.bh;
     net.n_ppt = f.bt + f.btile;
-    wgrid[&net == &critic ? 1 : 0] = f.bh + f.bt + f.btile;
-    wbh[&net == &critic ? 1 : 0] = f.bh;
+    wgrid[net.id] = f.bh + f.bt + f.btile;
+    wbh[net.id] = f.bh;
     if (sharded()) sum_partials(net.pph, f.bh, pn + 2 + slot, cur);  // the heads' |p|^2, all-reduced later
   }
 
@@ -1334,8 +1356,8 @@ struct mtsac_engine {
     adam_fused(hr, tr, tp, g, cur);
     net.n_pph = g.bh;
     net.n_ppt = g.bt + g.btile;
-    wgrid[&net == &critic ? 1 : 0] = g.bh + g.bt + g.btile;
-    wbh[&net == &critic ? 1 : 0] = g.bh;
+    wgrid[net.id] = g.bh + g.bt + g.btile;
+    wbh[net.id] = g.bh;
     if (sharded()) sum_partials(net.pph, g.bh, pn + 2 + slot, cur);
   }
 
@@ -1356,11 +1378,10 @@ struct mtsac_engine {
     a.sc = net.sc;
     a.np = np;
     if (h2) {
-      const int w = &net == &critic ? 1 : 0;
       a.h2.wrec = w_rec(net, 0).d;
       a.h2.trec = polyak ? w_rec(net, 1).d : nullptr;
       a.h2.w_add = adam_step_bound() * lr;
-      a.h2.wparts = wparts[w];
+      a.h2.wparts = wparts[net.id];
       a.h2.tparts = polyak ? tparts : nullptr;
     }
     a.n = net.trunk_off;  // heads
@@ -1502,19 +1523,19 @@ struct mtsac_engine {
   // pre_join (may be empty): segments issued after the last weight grad and before the join that
   // waits for the all-reduce buckets (the split actor forward, beside the critic's collective)
   template <class PJ = void (*)()>
-  int backward_segs(Net& net, const float* params, const float* X, int ldx, float** acts, __bf16** actp, float** dz,
-                    __bf16** dzp, int d_top, int w_prev, int M, PJ pre_join = [] {}) {
+  int backward_segs(Net& net, const float* params, const TrunkIn& in, const ActSet& a, const GradSet& dz, int d_top,
+                    int w_prev, int M, PJ pre_join = [] {}) {
     int dprev = d_top, wprev = w_prev, rprev = -1;
     const bool bucket = sharded() && net.depth > 1;
     for (int i = net.depth - 1; i >= 0; --i) {
-      wprev = seg({dprev, wprev}, 3, [&, i] { wgrad_layer(net, X, ldx, acts, actp, dz, dzp, i, M); });
+      wprev = seg({dprev, wprev}, 3, [&, i] { wgrad_layer(net, in, a, dz, i, M); });
       if (bucket && i > 0) {
         const long long b = net.off_b[i], e = (i + 1 < net.depth) ? net.off_b[i + 1] : net.n_flat;
         const int op = zero_of(net) ? 1 : 0;  // the sharded optimizer reduce-scatters
         rprev = rprev < 0 ? seg({wprev}, 4, [&, b, e, op] { coll(op, net.g + b, (size_t)(e - b)); })
                           : seg({wprev, rprev}, 4, [&, b, e, op] { coll(op, net.g + b, (size_t)(e - b)); });
       }
-      if (i > 0) dprev = seg({dprev}, 1, [&, i] { dgrad_layer(net, params, acts, actp, dz, dzp, i, M); });
+      if (i > 0) dprev = seg({dprev}, 1, [&, i] { dgrad_layer(net, params, a, dz, i, M); });
     }
     pre_join();
     if (rprev >= 0) return seg({dprev, wprev, rprev}, 1, [] {});  // join point
@@ -1552,10 +1573,7 @@ struct mtsac_engine {
     task = inset[k].task;
     counts = inset[k].counts;
     rows = inset[k].rows;
-    // the planes alternate with xa: the input-layer weight grad of step k's actor backward reads
-    // them (on k-major planes below 4096 rows) after s_ap, while step k + 1's gather writes the other set
-    inp[0].x = xa;
-    inp[0].p = inset[k].xap;
+    // in() follows: step k's actor backward reads xa's planes after s_ap; step k + 1's gather writes the other set
   }
 
   // ---- the head / loss kernels' parameter blocks, shared by step() and the per-task gradient passes
@@ -1626,6 +1644,54 @@ struct mtsac_engine {
     ag.dout = dout_a;
     return ag;
   }
+  // The critic head's three blocks over a pass's base `ch`.  The TD target y from the target critic's top
+  // activations: a launch of its own, or (ch_critic's fused_target) riding in the critic loss launch.  The
+  // two losses write dq, under dq_rec (split2h; null: a pass on fp32 operands); inv_norm: the mean they take
+  CriticHeadParams ch_target(CriticHeadParams c) {
+    c.head = head(critic, critic.tgt, hct[critic.depth - 1], B, task);
+    c.mode = CH_TARGET;
+    c.logpi = logpi_n;
+    c.y_out = y;
+    return c;
+  }
+  CriticHeadParams ch_loss(CriticHeadParams c, int mode, const HeadParams& chp, float inv_norm, RecRef* dq_rec) {
+    c.head = chp;
+    c.mode = mode;
+    c.dq = dq;
+    c.inv_norm = inv_norm;
+    c.dq_rec = dq_rec ? dq_rec->d : nullptr;
+    c.dq_parts = dq_rec ? &dq_rec->n : nullptr;
+    return c;
+  }
+  CriticHeadParams ch_critic(CriticHeadParams c, const HeadParams& chp, float inv_norm, bool fused_target,
+                             RecRef* dq_rec) {
+    if (fused_target) {  // the target's head, logpi and y_out ride along
+      c = ch_target(c);
+      c.thead = c.head;
+      c.fused_target = 1;
+    }
+    c.y = y;
+    c.row_a = row_a;
+    c.row_b = row_b;
+    return ch_loss(c, CH_CRITIC, chp, inv_norm, dq_rec);
+  }
+  CriticHeadParams ch_actor(CriticHeadParams c, const HeadParams& chp, float inv_norm, RecRef* dq_rec) {
+    c.logpi = logpi;
+    c.row_a = row_c;
+    c.alpha_w = alpha_w;
+    return ch_loss(c, CH_ACTOR, chp, inv_norm, dq_rec);
+  }
+  // the batch (a replay sample, or the uploaded user batch) into the input buffers; row lists: the caller's
+  void load_batch(bool device_batch) {
+    GatherParams gp = gather_params();
+    if (device_batch) {
+      replay_indices(rng, jump, buf_size, n, idx, cur);
+      replay_gather(gp, cur);
+    } else {
+      if (h2) user_batch_max(gp, B);
+      batch_scatter(gp, u_obs, u_act, u_nobs, u_done, u_rew, B, cur);
+    }
+  }
 
   // pipelined: eager issue that overlaps the previous step's tail (see InSet); join: the main
   // stream waits for every lane at the end (the last step of a call, and every non-pipelined one)
@@ -1657,21 +1723,14 @@ struct mtsac_engine {
     }
     pf_issue = overlap && p2;
     const int s_in = seg({}, 0, [&] {
-      GatherParams gp = gather_params();
-      if (device_batch) {
-        replay_indices(rng, jump, buf_size, n, idx, cur);
-        replay_gather(gp, cur);
-      } else {
-        if (h2) user_batch_max(gp, Bl);
-        batch_scatter(gp, u_obs, u_act, u_nobs, u_done, u_rew, Bl, cur);
-        task_rows(task, Bl, T_l, counts, rows, Bl, cur);  // a user batch: lists from its task ids
-      }
+      load_batch(device_batch);
+      if (!device_batch) task_rows(task, Bl, T_l, counts, rows, Bl, cur);  // a user batch: lists from its task ids
       if (cfg.use_task_weights) row_alpha(task, cfg.task_begin, log_alpha, T_g, Bl, 1, row_c, tw, cur);
     });
     // critic forward on (s, a) with the current critic (mtsac.py:555); pipelined on lane 2, which
     // the previous step's tail (lanes 1, 3, 4) does not use, so it runs beside that tail
     const bool ol = overlap || lanes_alt;
-    const int s_cf = seg({s_in}, ol ? 2 : 1, [&] { trunk_forward(critic, critic.p, 0, xc, ld_c, hc, hcp, Bl); });
+    const int s_cf = seg({s_in}, ol ? 2 : 1, [&] { trunk_forward(critic, critic.p, 0, in().c, acts_c, Bl); });
     pf_issue = false;
     if (overlap && !p2) (void)hipStreamWaitEvent(st, ev_tail[step_par ^ 1], 0);  // s_af: the updated actor
     // ONE actor forward over [s | s'] with the pre-update actor: update_critic samples a' ~ pi(.|s')
@@ -1688,17 +1747,18 @@ struct mtsac_engine {
     auto step_pi = [&](bool next) {
       PolicyParams q = next ? pi_next(pp, han[actor.depth - 1], device_noise) : pi_s(pp, ha[actor.depth - 1], device_noise);
       q.stream_id = next ? 1 : 2;
-      q.a_planes = in_planes(next ? xcn : xcp);
-      q.ap_rec = h2 ? r_in[inset_cur].d : nullptr;
+      const TrunkIn& xq = next ? in().cn : in().cp;
+      q.a_planes = xq.p;
+      q.ap_rec = h2 ? xq.rec->d : nullptr;
       return q;
     };
     const int s_af = seg({s_in}, ol ? 0 : 2, [&] {
       if (split_af) {  // the s' rows only: a' ~ pi(.|s') for the TD target
-        trunk_forward(actor, actor.p, 0, xan, ld_a, han, hap_s2, Bl);
+        trunk_forward(actor, actor.p, 0, in().an, acts_an, Bl);
         policy_head(step_pi(true), cur);
         return;
       }
-      trunk_forward(actor, actor.p, 0, xa, ld_a, ha, hap, Ma);
+      trunk_forward(actor, actor.p, 0, in().a, acts_a, Ma);
       policy_head_pair(step_pi(false), step_pi(true), cur);
       if (snap_on)
         (void)hipMemcpyAsync(dbg_snap[0], ha[actor.depth - 1], sizeof(float) * Ma * actor.width,
@@ -1707,41 +1767,17 @@ struct mtsac_engine {
     // target critic at (s', a'), TD target (mtsac.py:529-553)
     const bool fuse_td = one_stream || timing_serial;  // lanes: s_tg and s_cf run on two lanes
     const int s_tg = seg({s_af}, 0, [&] {
-      trunk_forward(critic, critic.tgt, 1, xcn, ld_c, hct, hctp, Bl);
-      if (!fuse_td) {  // one stream: the TD target rides in the critic loss launch (s_cl)
-        CriticHeadParams c = ch;
-        c.head = head(critic, critic.tgt, hct[critic.depth - 1], Bl, task);
-        c.mode = CH_TARGET;
-        c.logpi = logpi_n;
-        c.y_out = y;
-        critic_head(c, cur);
-      }
+      trunk_forward(critic, critic.tgt, 1, in().cn, acts_ct, Bl);
+      if (!fuse_td) critic_head(ch_target(ch), cur);  // one stream: it rides in the critic loss launch (s_cl)
     });
     // critic loss (mtsac.py:538-566) and head backward
     const HeadParams chp = head(critic, critic.p, hc[critic.depth - 1], Bl, task);
+    RecRef* const dq_rec = h2 ? &r_dq : nullptr;
     bool c_both = false;  // the critic head's weight grad went with its data pass (one launch)
     const int s_cl = seg({s_cf, s_tg}, 1, [&] {
-      CriticHeadParams c = ch;
-      c.head = chp;
-      c.mode = CH_CRITIC;
-      c.y = y;
-      if (fuse_td) {
-        c.fused_target = 1;
-        c.thead = head(critic, critic.tgt, hct[critic.depth - 1], Bl, task);
-        c.logpi = logpi_n;
-        c.y_out = y;
-      }
-      c.dq = dq;
-      c.row_a = row_a;
-      c.row_b = row_b;
-      c.inv_norm = 1.0f / ((float)critic.E * (float)B_glob);
-      if (h2) {
-        c.dq_rec = r_dq.d;
-        c.dq_parts = &r_dq.n;
-      }
-      critic_head(c, cur);
-      c_both = head_bwd_both(critic, chp, dq, Bl, dzcp, true);
-      if (!c_both) head_bwd(critic, chp, dq, Bl, dzc, dzcp, true);
+      critic_head(ch_critic(ch, chp, 1.0f / ((float)critic.E * (float)B_glob), fuse_td, dq_rec), cur);
+      c_both = head_bwd_both(critic, chp, dq, Bl, grads_c, true);
+      if (!c_both) head_bwd(critic, chp, dq, Bl, grads_c, true);
       if (sharded()) {  // the loss sums ride in the all-reduced scalar tail (else: step_finish)
         const float* ins[2] = {row_a, row_b};
         reduce_rows(ins, 2, Bl, critic.g + critic.n_flat + 1, cur);
@@ -1751,10 +1787,10 @@ struct mtsac_engine {
       if (!c_both) head_wgrad(critic, chp, dq, Bl);
     });
     int s_afs = s_af;
-    const int s_cb = backward_segs(critic, critic.p, xc, ld_c, hc, hcp, dzc, dzcp, s_cl, s_chw, Bl, [&] {
+    const int s_cb = backward_segs(critic, critic.p, in().c, acts_c, grads_c, s_cl, s_chw, Bl, [&] {
       if (split_af)  // the s rows beside the critic's all-reduce
         s_afs = seg({s_in}, 1, [&] {
-          trunk_forward(actor, actor.p, 0, xa, ld_a, ha, hap, Bl);
+          trunk_forward(actor, actor.p, 0, in().a, acts_a, Bl);
           policy_head(step_pi(false), cur);
         });
     });
@@ -1762,32 +1798,19 @@ struct mtsac_engine {
     const int s_co = seg({s_cb}, 1, [&] {
       if (sharded()) head_sq(critic);  // the heads' |g|^2 into the all-reduced scalar tail
       reduce_rest(critic);
-      optimize(critic, cfg.critic_lr, cfg.critic_max_grad_norm, true, 0);
+      optimize(critic, critic.lr, cfg.critic_max_grad_norm, true, 0);
       refresh_wt(critic, critic.p, 0, cur, true);
       refresh_wt(critic, critic.tgt, 1, cur, true);
     });
     // actor loss through the UPDATED critic (mtsac.py:659-691)
     const int s_ap = seg({s_co, s_af, s_afs}, 1, [&] {
-      trunk_forward(critic, critic.p, 0, xcp, ld_c, hc, hcp, Bl);
-      CriticHeadParams c = ch;
-      c.head = head(critic, critic.p, hc[critic.depth - 1], Bl, task);
-      c.mode = CH_ACTOR;
-      c.logpi = logpi;
-      c.dq = dq;
-      c.row_a = row_c;
-      c.alpha_w = alpha_w;
-      c.inv_norm = 1.0f / (float)B_glob;
-      if (h2) {
-        c.dq_rec = r_dq.d;
-        c.dq_parts = &r_dq.n;
-      }
-      critic_head(c, cur);
+      trunk_forward(critic, critic.p, 0, in().cp, acts_c, Bl);
+      critic_head(ch_actor(ch, chp, 1.0f / (float)B_glob, dq_rec), cur);
       const bool rag = actor_compact(Bl);  // each member's rows with dq != 0 only
       actor_compact_last = rag ? 1 : 0;
       if (rag) active_rows(dq, critic.E, Bl, act_n, act_rows, act_slot, cur);
-      head_bwd(critic, c.head, dq, Bl, dzc, dzcp, false, rag ? act_slot : nullptr);
-      for (int i = critic.depth - 1; i > 0; --i)
-        dgrad_layer(critic, critic.p, hc, hcp, dzc, dzcp, i, Bl, false, rag);
+      head_bwd(critic, chp, dq, Bl, grads_c, false, rag ? act_slot : nullptr);
+      for (int i = critic.depth - 1; i > 0; --i) dgrad_layer(critic, critic.p, acts_c, grads_c, i, Bl, false, rag);
       ActionGradParams ag = action_grad_params();
       ag.slot = rag ? act_slot : nullptr;
       if (h2) {
@@ -1806,21 +1829,21 @@ struct mtsac_engine {
     if (pipelined) (void)hipEventRecord(ev_ap[step_par], segs[s_ap].lane);
     const HeadParams ahp = head(actor, actor.p, ha[actor.depth - 1], Bl, task);
     // the head's data and weight passes in one launch (head_bwd_both's conditions)
-    const bool a_both = top_planes(actor, dzap).p != nullptr && actor.width % 4 == 0 && !actor.shared;
+    const bool a_both = top_planes(actor, grads_a).p != nullptr && actor.width % 4 == 0 && !actor.shared;
     const int s_ahw = seg({s_ap}, 3, [&] {
       if (!a_both) head_wgrad(actor, ahp, dout_a, 0);
     });
     const int s_ad = seg({s_ap}, 1, [&] {
-      if (!(a_both && head_bwd_both(actor, ahp, dout_a, 0, dzap, true))) head_bwd(actor, ahp, dout_a, 0, dza, dzap, true);
+      if (!(a_both && head_bwd_both(actor, ahp, dout_a, 0, grads_a, true))) head_bwd(actor, ahp, dout_a, 0, grads_a, true);
     });
-    const int s_ab = backward_segs(actor, actor.p, xa, ld_a, ha, hap, dza, dzap, s_ad, s_ahw, Bl);
+    const int s_ab = backward_segs(actor, actor.p, in().a, acts_a, grads_a, s_ad, s_ahw, Bl);
     const int s_tail = seg({s_ab}, 1, [&] {
       // temperature gradient rides in the actor's scalar tail: [2] loss part, [3..] grad
       AlphaParams al = alpha_params();
       if (sharded()) alpha_grad(al, cur);  // unsharded: inside step_finish
       if (sharded()) head_sq(actor);
       reduce_rest(actor);
-      optimize(actor, cfg.actor_lr, cfg.actor_max_grad_norm, false, 1);
+      optimize(actor, actor.lr, cfg.actor_max_grad_norm, false, 1);
       refresh_wt(actor, actor.p, 0, cur, true);
       // temperature (mtsac.py:713-731), post-update parameter norms (trunk |p|^2 replicated, head
       // |p|^2 summed over shards), logs: one launch
@@ -1862,10 +1885,9 @@ struct mtsac_engine {
   int ensure_task_grad_buffers() {
     int rc = 0;
     for (int w = 0; w < 2; ++w) {
-      const Net& net = w == 0 ? critic : actor;
-      tgP[w] = net.n_params;
-      if (!tg[w] && (rc = alloc(&tg[w], (size_t)T_l * tgP[w]))) return rc;
       Net& nw = w == 0 ? critic : actor;
+      tgP[w] = nw.n_params;
+      if (!tg[w] && (rc = alloc(&tg[w], (size_t)T_l * tgP[w]))) return rc;
       if (nw.shared && !nw.tgh && (rc = alloc(&nw.tgh, (size_t)nw.E * T_l * ((size_t)nw.width * nw.hd + nw.hd))))
         return rc;
     }
@@ -1881,16 +1903,16 @@ struct mtsac_engine {
   }
 
   // dW_t, db_t of trunk layer i for every task t (one batched TN GEMM per ensemble member)
-  void task_wgrad(Net& net, int w, const float* X, int ldx, float** acts, float** dz, int i) {
+  void task_wgrad(Net& net, int w, const TrunkIn& in, const ActSet& a, const GradSet& dz, int i) {
     const std::vector<long long>& off = net.dense;
     const int fan = i == 0 ? net.in_dim : net.width;
     const int n_rows = B / T_l;
     for (int e = 0; e < net.E; ++e) {
       GemmParams g{};
-      g.A = i == 0 ? X : acts[i - 1] + (long long)e * B * net.width;
-      g.lda = (i == 0 ? ldx : net.width) * T_l;
-      g.sA = i == 0 ? ldx : net.width;
-      g.B = dz[i] + (long long)e * B * net.width;
+      g.A = i == 0 ? in.x : a.f[i - 1] + (long long)e * B * net.width;
+      g.lda = (i == 0 ? in.ld : net.width) * T_l;
+      g.sA = i == 0 ? in.ld : net.width;
+      g.B = dz.f[i] + (long long)e * B * net.width;
       g.ldb = net.width * T_l;
       g.sB = net.width;
       g.C = tg[w] + off[net.lk_W(i)] + (long long)e * fan * net.width;
@@ -1943,14 +1965,7 @@ struct mtsac_engine {
     cur_lane = 0;
     counts = inset[inset_cur].counts;  // task_rows below (check_interleaved holds the layout)
     rows = inset[inset_cur].rows;
-    GatherParams gp = gather_params();
-    if (device_batch) {
-      replay_indices(rng, jump, buf_size, n, idx, cur);
-      replay_gather(gp, cur);
-    } else {
-      if (h2) user_batch_max(gp, Bl);
-      batch_scatter(gp, u_obs, u_act, u_nobs, u_done, u_rew, Bl, cur);
-    }
+    load_batch(device_batch);
     check_interleaved(task, Bl, T_l, err, cur);
     task_rows(task, Bl, T_l, counts, rows, Bl, cur);
     if (cfg.use_task_weights) row_alpha(task, cfg.task_begin, log_alpha, T_g, Bl, 1, row_c, tw, cur);
@@ -1973,43 +1988,26 @@ struct mtsac_engine {
     const int Dc = critic.depth, Da = actor.depth;
 
     // ---- critic (mtsac.py:1000-1048): a_n ~ pi(.|s), y from the target critic at (s', a_n)
-    trunk_forward(actor, actor.p, 0, xa, ld_a, han, nullptr, Bl);
+    trunk_forward(actor, actor.p, 0, in().a, acts_an.f32(), Bl);
     {
       PolicyParams q = pi_next(pp, han[Da - 1], device_noise);
       q.stream_id = pc ? 5 : 3;
       q.noise_div = pc ? T_l : 0;
       policy_head(q, cur);
     }
-    trunk_forward(critic, critic.tgt, 1, xcn, ld_c, hct, nullptr, Bl);
-    {
-      CriticHeadParams c = ch;
-      c.head = head(critic, critic.tgt, hct[Dc - 1], Bl, task);
-      c.mode = CH_TARGET;
-      c.logpi = logpi_n;
-      c.y_out = y;
-      critic_head(c, cur);
-    }
-    trunk_forward(critic, critic.p, 0, xc, ld_c, hc, nullptr, Bl);
+    trunk_forward(critic, critic.tgt, 1, in().cn, acts_ct.f32(), Bl);
+    critic_head(ch_target(ch), cur);
+    trunk_forward(critic, critic.p, 0, in().c, acts_c.f32(), Bl);
     const HeadParams chp = head(critic, critic.p, hc[Dc - 1], Bl, task);
-    {
-      CriticHeadParams c = ch;
-      c.head = chp;
-      c.mode = CH_CRITIC;
-      c.y = y;
-      c.dq = dq;
-      c.row_a = row_a;
-      c.row_b = row_b;
-      c.inv_norm = 1.0f / ((float)critic.E * (float)n_rows);  // per-task mean over E x n
-      critic_head(c, cur);
-    }
+    // per-task mean over E x n
+    critic_head(ch_critic(ch, chp, 1.0f / ((float)critic.E * (float)n_rows), false, nullptr), cur);
     head_backward_data(chp, dq, Bl, dzc[Dc - 1], counts, rows, Bl, T_l, cur);
     task_head_wgrad(critic, chp, dq, Bl);
     task_heads(critic, 0);
     for (int i = Dc - 1; i >= 0; --i) {
-      task_wgrad(critic, 0, xc, ld_c, hc, dzc, i);
-      if (i > 0) dgrad_layer(critic, critic.p, hc, nullptr, dzc, nullptr, i, Bl);
+      task_wgrad(critic, 0, in().c, acts_c.f32(), grads_c.f32(), i);
+      if (i > 0) dgrad_layer(critic, critic.p, acts_c.f32(), grads_c.f32(), i, Bl);
     }
-
   }
 
   void tg_actor(bool device_noise, bool pc) {
@@ -2019,27 +2017,18 @@ struct mtsac_engine {
     head_base(pp, ch, n_rows, 0, 0);
     const int Dc = critic.depth, Da = actor.depth;
     // ---- actor (mtsac.py:1051-1090): the current critic, per-task mean over n rows
-    trunk_forward(actor, actor.p, 0, xa, ld_a, ha, nullptr, Bl);
+    trunk_forward(actor, actor.p, 0, in().a, acts_a.f32(), Bl);
     {
       PolicyParams q = pi_s(pp, ha[Da - 1], device_noise);
       q.stream_id = pc ? 6 : 4;
       q.noise_div = pc ? T_l : 0;
       policy_head(q, cur);
     }
-    trunk_forward(critic, critic.p, 0, xcp, ld_c, hc, nullptr, Bl);
-    {
-      CriticHeadParams c = ch;
-      c.head = head(critic, critic.p, hc[Dc - 1], Bl, task);
-      c.mode = CH_ACTOR;
-      c.logpi = logpi;
-      c.dq = dq;
-      c.row_a = row_c;
-      c.alpha_w = alpha_w;
-      c.inv_norm = 1.0f / (float)n_rows;
-      critic_head(c, cur);
-      head_backward_data(c.head, dq, Bl, dzc[Dc - 1], counts, rows, Bl, T_l, cur);
-    }
-    for (int i = Dc - 1; i > 0; --i) dgrad_layer(critic, critic.p, hc, nullptr, dzc, nullptr, i, Bl);
+    trunk_forward(critic, critic.p, 0, in().cp, acts_c.f32(), Bl);
+    const HeadParams chp = head(critic, critic.p, hc[Dc - 1], Bl, task);
+    critic_head(ch_actor(ch, chp, 1.0f / (float)n_rows, nullptr), cur);
+    head_backward_data(chp, dq, Bl, dzc[Dc - 1], counts, rows, Bl, T_l, cur);
+    for (int i = Dc - 1; i > 0; --i) dgrad_layer(critic, critic.p, acts_c.f32(), grads_c.f32(), i, Bl);
     {
       ActionGradParams ag = action_grad_params();
       if (pc) {  // mtsac.py:668-673 with the default _explore = True of the split call (:678-682)
@@ -2056,8 +2045,8 @@ struct mtsac_engine {
     task_head_wgrad(actor, ahp, dout_a, 0);
     task_heads(actor, 1);
     for (int i = Da - 1; i >= 0; --i) {
-      task_wgrad(actor, 1, xa, ld_a, ha, dza, i);
-      if (i > 0) dgrad_layer(actor, actor.p, ha, nullptr, dza, nullptr, i, Bl);
+      task_wgrad(actor, 1, in().a, acts_a.f32(), grads_a.f32(), i);
+      if (i > 0) dgrad_layer(actor, actor.p, acts_a.f32(), grads_a.f32(), i, Bl);
     }
   }
 
@@ -2111,20 +2100,19 @@ struct mtsac_engine {
     PolicyParams pp;
     CriticHeadParams ch;
     head_base(pp, ch, B / T_l, 0, 0);  // fp32 operands: no action planes
-    trunk_forward(actor, actor.p, 0, xa, ld_a, ha, nullptr, Bl);
+    trunk_forward(actor, actor.p, 0, in().a, acts_a.f32(), Bl);
     {
       PolicyParams q = pi_s(pp, ha[actor.depth - 1], device_noise);
       q.stream_id = 4;  // the position tg_actor draws a ~ pi(.|s) from
       policy_head(q, cur);
     }
-    trunk_forward(critic, critic.p, 0, xcp, ld_c, hc, nullptr, Bl);
+    trunk_forward(critic, critic.p, 0, in().cp, acts_c.f32(), Bl);
     (void)hipEventRecord(nm.ev[0], cur);
     for (int w = 0; w < 2 && (what & 1); ++w) {
       const Net& net = nm_net(w);
-      float** acts = w == 0 ? ha : hc;
       for (int i = 0; i < net.depth; ++i) {
         ActStats s{};
-        s.H = acts[i];
+        s.H = acts_of(net).f[i];
         s.Z = net.E;
         s.M = Bl;
         s.W = net.width;
@@ -2144,11 +2132,10 @@ struct mtsac_engine {
     (void)hipEventRecord(nm.ev[1], cur);
     for (int w = 0; w < 2 && (what & 2); ++w) {
       const Net& net = nm_net(w);
-      float** acts = w == 0 ? ha : hc;
       const long long rr = (long long)nm_dim(w) * nm_dim(w);
       for (int i = 0; i < net.depth; ++i) {
         ActGram g{};
-        g.H = acts[i];
+        g.H = acts_of(net).f[i];
         g.Z = net.E;
         g.M = Bl;
         g.W = net.width;
@@ -2430,14 +2417,14 @@ struct mtsac_engine {
     clear_task_heads(critic, 0);
     tg_critic(device_noise, true);
     surgery_of(critic, 0);
-    optimize(critic, cfg.critic_lr, cfg.critic_max_grad_norm, true, 0);
+    optimize(critic, critic.lr, cfg.critic_max_grad_norm, true, 0);
     refresh_wt(critic, critic.p, 0, cur, true);
     refresh_wt(critic, critic.tgt, 1, cur, true);
     // actor through the UPDATED critic (mtsac.py:623-711)
     clear_task_heads(actor, 1);
     tg_actor(device_noise, true);
     surgery_of(actor, 1);
-    optimize(actor, cfg.actor_lr, cfg.actor_max_grad_norm, false, 1);
+    optimize(actor, actor.lr, cfg.actor_max_grad_norm, false, 1);
     refresh_wt(actor, actor.p, 0, cur, true);
     // temperature, parameter norms, logs; then the slots the surgery changes: the gradient magnitudes
     // are the pre-surgery |mean_t g_t| (the optimizer's clip saw the combined gradient's norm)
@@ -2505,17 +2492,17 @@ struct mtsac_engine {
     gp.norm_eps = cfg.normalize_rewards == 2 ? 0.0 : 1e-8;
     gp.err = err;
     if (h2) {
-      gp.in_rec = r_in[inset_cur].d;
+      gp.in_rec = in().a.rec->d;
       gp.in_max = bufmax;
     }
     if (planes) {
-      gp.pa = inp[0].p;
+      gp.pa = in().a.p;
       gp.pa_ps = actor.arows * actor.xld;
       gp.pa_ld = (int)actor.xld;
       gp.pa_next = actor.krows;
-      gp.pc = in_planes(xc);
-      gp.pcn = in_planes(xcn);
-      gp.pcp = in_planes(xcp);
+      gp.pc = in().c.p;
+      gp.pcn = in().cn.p;
+      gp.pcp = in().cp.p;
       gp.pc_ps = critic.arows * critic.xld;
       gp.pc_ld = (int)critic.xld;
     }
@@ -2727,6 +2714,8 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
 
   e->actor.layout(e->D, e->ld_a, c.actor_width, c.actor_depth, e->T_l, 2 * e->A, 1, shared);
   e->critic.layout(e->D + e->A, e->ld_c, c.critic_width, c.critic_depth, e->T_l, 1, c.num_critics, shared);
+  e->actor.bind(NET_ACTOR, c.actor_lr, &e->r_dout);
+  e->critic.bind(NET_CRITIC, c.critic_lr, &e->r_dq);
   for (Net* net : {&e->actor, &e->critic}) {
     if (shared && (rc = e->alloc(&net->hws, (size_t)head_shared_ws_floats(e->B, net->width, net->hd, net->E))))
       return bad(rc);
@@ -2767,7 +2756,7 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
     net->ald = align_up(net->width, 32);
     net->xld = align_up(net->in_dim, 32);
     net->krows = align_up(e->B, 32);
-    net->arows = net == &e->actor ? align_up(net->krows + e->B, 32) : net->krows;
+    net->arows = net->id == NET_ACTOR ? align_up(net->krows + e->B, 32) : net->krows;
     // row-major x row-major plane GEMMs for the trunk forward and data grad (hidden activations
     // then keep planes only): gemm_x3f when its 208 x 256 tiles fill the chip (with split-K when
     // they do not), gemm_x3s for narrow trunks (K <= 512: W = 400).  The 16 TI x 64 tiles of
@@ -2781,7 +2770,7 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
       const char* v = getenv("MTSAC_X3F_MIN_TILES");
       return v ? atoi(v) : 64;
     }();
-    const int M_fwd = net == &e->actor ? (int)(net->krows + e->B) : e->B;  // the actor forward's rows
+    const int M_fwd = net->id == NET_ACTOR ? (int)(net->krows + e->B) : e->B;  // the actor forward's rows
     net->x3f = e->planes && net->depth > 1 &&
                ((net->ald % 64 == 0 && gemm_x3f_tiles(M_fwd, net->width, net->E) >= x3f_min_tiles) ||
                 (net->ald <= 512 && e->B <= 2048));
@@ -2795,7 +2784,7 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
     const bool cand = net->x3f && bfrag_req != 0 && net->depth <= MAX_TILE_LEAVES && net->width % 16 == 0 &&
                       net->ald % 64 == 0 && net->wld % 32 == 0;
     for (int i = 0; i < net->depth; ++i) net->bfrag[i] = cand;
-    for (int w = 0; w < (net == &e->critic ? 2 : 1); ++w)
+    for (int w = 0; w < (net->id == NET_CRITIC ? 2 : 1); ++w)  // the critic's Polyak target too
       for (int i = 0; i < net->depth; ++i) {
         if (!e->planes) {
           if (i > 0 && (rc = e->alloc(&net->wt[w][i], (size_t)net->ms_W[i] * net->E))) return bad(rc);
@@ -2804,7 +2793,7 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
         if ((rc = e->alloc(&net->wp[w][i], (size_t)net->E * 3 * net->kps(i)))) return bad(rc);
         if (net->x3f && (rc = e->alloc(&net->wtp[w][i], (size_t)net->E * 3 * net->wtps(i)))) return bad(rc);
       }
-    if (net == &e->actor && net->E == 1 && net->width % 4 == 0 &&
+    if (net->id == NET_ACTOR && net->E == 1 && net->width % 4 == 0 &&
         (rc = e->alloc(&net->whT, (size_t)net->Th * net->width * net->hd)))
       return bad(rc);
   }
@@ -2818,16 +2807,16 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
       ws = std::max(ws, gemm_x3f_ws_floats(g.M, g.N, (int)align_up(g.K, 64), batch));
     };
     for (Net* net : {&e->actor, &e->critic}) {
-      const bool ac = net == &e->actor;
-      float **acts = ac ? e->ha : e->hc, **dz = ac ? e->dza : e->dzc;
-      __bf16 **actp = ac ? e->hap : e->hcp, **dzp = ac ? e->dzap : e->dzcp;
+      const TrunkIn& in = e->in_of(*net);
+      const ActSet& a = e->acts_of(*net);
+      const GradSet& dz = e->grads_of(*net);
       for (int i = 0; i < net->depth; ++i) {
         const int M = i == 0 ? net->in_dim : net->width;  // the fp32 weight grad
         ws = std::max(ws, gemm_ws_floats(M, net->width, net->E, gemm_splits(M, net->width, e->B, net->E)));
         if (!e->planes) continue;
-        for (int rows : {e->B, ac ? e->Ma : e->B}) fd(e->fwd_params(*net, net->p, 0, nullptr, acts, actp, i, rows), net->E);
-        if (i > 0) fd(e->dgrad_params(*net, acts, actp, dz, dzp, i, e->B, true), net->E);
-        const SplitGemmParams wg = e->wgrad_params(*net, nullptr, actp, dzp, i);
+        for (int rows : {e->B, e->fwd_rows(*net)}) fd(e->fwd_params(*net, net->p, 0, in, a, i, rows), net->E);
+        if (i > 0) fd(e->dgrad_params(*net, a, dz, i, e->B, true), net->E);
+        const SplitGemmParams wg = e->wgrad_params(*net, in, a, dz, i);
         const long long w = gemm_x3p_ws_floats(wg.M, wg.N, wg.K, net->E, true);
         ws = std::max(ws, w);  // sharded (or MTSAC_DEFER_FINISH=0): its slabs go to the lane workspace
         // the deferred finishes' slabs, per layer (Net::fin_sink); sharded runs never use them, but
@@ -2871,6 +2860,15 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
   if ((rc = e->alloc(&e->xc, (size_t)B * e->ld_c))) return bad(rc);
   if ((rc = e->alloc(&e->xcn, (size_t)B * e->ld_c))) return bad(rc);
   if ((rc = e->alloc(&e->xcp, (size_t)B * e->ld_c))) return bad(rc);
+  for (int k = 0; k < 2; ++k) {  // each set's trunk inputs; their planes, where the precision has them, below
+    mtsac_engine::InSet& q = e->inset[k];
+    RecRef* const r = &e->r_in[k];
+    q.a = TrunkIn{q.xa, e->ld_a, nullptr, r};
+    q.an = TrunkIn{q.xa + e->actor.krows * e->ld_a, e->ld_a, nullptr, r};
+    q.c = TrunkIn{e->xc, e->ld_c, nullptr, r};
+    q.cn = TrunkIn{e->xcn, e->ld_c, nullptr, r};
+    q.cp = TrunkIn{e->xcp, e->ld_c, nullptr, r};
+  }
   for (float** p : {&e->rew, &e->done, &e->tw, &e->logpi_n, &e->logpi, &e->y, &e->row_a, &e->row_b, &e->row_c,
                     &e->alpha_w, &e->u_done, &e->u_rew})
     if ((rc = e->alloc(p, B))) return bad(rc);
@@ -2890,7 +2888,7 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
       if ((rc = e->alloc(p, (size_t)c.num_critics * B * c.critic_width))) return bad(rc);
   if (e->planes) {
     for (Net* net : {&e->actor, &e->critic}) {
-      const bool cr = net == &e->critic;
+      const bool cr = net->id == NET_CRITIC;
       const size_t np = (size_t)net->E * 3 * net->aps();
       for (int i = 0; i + 1 < net->depth; ++i) {
         if ((rc = e->alloc(cr ? &e->hcp[i] : &e->hap[i], np))) return bad(rc);
@@ -2907,16 +2905,17 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
       for (int i = d0; i < net->depth; ++i)
         if ((rc = e->alloc(&net->dbp[i], (size_t)(net->E * chunks * net->width)))) return bad(rc);
     }
-    {
-      const float* xs[5] = {e->xa, e->xan, e->xc, e->xcn, e->xcp};
-      for (int k = 0; k < 5; ++k) {
-        const Net& net = k < 2 ? e->actor : e->critic;
-        if (k == 1) continue;  // s' rows are part of xa's planes (the merged actor forward)
-        e->inp[k].x = xs[k];
-        if ((rc = e->alloc(&e->inp[k].p, (size_t)3 * net.arows * net.xld))) return bad(rc);
-      }
-      e->inset[0].xap = e->inp[0].p;  // the second input set's planes (cross-step pipelining)
-      if ((rc = e->alloc(&e->inset[1].xap, (size_t)3 * e->actor.arows * e->actor.xld))) return bad(rc);
+    {  // planes of the GEMM-ready trunk inputs, [3][arows][xld]: xa's per input set (cross-step pipelining;
+       // the s' rows are part of them: the merged actor forward), xc / xcn / xcp's shared by the sets
+      mtsac_engine::InSet &q0 = e->inset[0], &q1 = e->inset[1];
+      const size_t na = (size_t)3 * e->actor.arows * e->actor.xld, nc = (size_t)3 * e->critic.arows * e->critic.xld;
+      if ((rc = e->alloc(&q0.a.p, na)) || (rc = e->alloc(&q0.c.p, nc)) || (rc = e->alloc(&q0.cn.p, nc)) ||
+          (rc = e->alloc(&q0.cp.p, nc)) || (rc = e->alloc(&q1.a.p, na)))
+        return bad(rc);
+      q1.c.p = q0.c.p;
+      q1.cn.p = q0.cn.p;
+      q1.cp.p = q0.cp.p;
+      for (mtsac_engine::InSet& q : e->inset) q.an.p = q.a.p + e->actor.krows * e->actor.xld;
     }
     const int wmax = std::max(c.actor_width, c.critic_width);
     if ((rc = e->alloc(&e->cs_part, (size_t)std::max(1, c.num_critics) * COLSUM_CHUNKS * wmax))) return bad(rc);
@@ -2952,6 +2951,7 @@ int mtsac_create_flags(const mtsac_config* cfg, uint32_t flags, int hip_device, 
   const int rm = e->roll_max;
   if ((rc = e->alloc(&e->r_obs, (size_t)rm * e->D))) return bad(rc);
   if ((rc = e->alloc(&e->r_x, (size_t)rm * e->ld_a))) return bad(rc);
+  e->in_r = TrunkIn{e->r_x, e->ld_a, nullptr, nullptr};
   if ((rc = e->alloc(&e->r_eps, (size_t)rm * e->A))) return bad(rc);
   if ((rc = e->alloc(&e->r_act, (size_t)rm * e->A))) return bad(rc);
   if ((rc = e->alloc(&e->r_lp, rm))) return bad(rc);
@@ -3929,7 +3929,7 @@ static int act(mtsac_engine* h, const float* obs, int n, const float* eps, float
   gp.err = h->err;
   // obs doubles as next_obs; the action / reward / done inputs are ignored scratch
   batch_scatter(gp, h->r_obs, h->r_eps, h->r_obs, h->r_lp, h->r_lp, n, h->st);
-  h->trunk_forward(h->actor, h->actor.p, -1, h->r_x, h->ld_a, h->r_h, nullptr, n);
+  h->trunk_forward(h->actor, h->actor.p, -1, h->in_r, h->acts_r, n);
   PolicyParams pp{};
   pp.head = h->head(h->actor, h->actor.p, h->r_h[h->actor.depth - 1], n, h->r_task);
   pp.eps = h->r_eps;
