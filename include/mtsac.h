@@ -201,6 +201,35 @@ int mtsac_rng_get(mtsac_engine* h, uint64_t* state_hi, uint64_t* state_lo, uint6
 int mtsac_sample(mtsac_engine* h, int64_t* indices, float* obs, float* actions, float* next_obs,
                  float* dones, float* rewards);
 
+/* ---- per-task batch sizes (MultiTaskReplayBuffer.sample with an array, mtrl/rl/buffers.py:494-519; the
+ * sizes the reference's Sampler / AdaptiveSampler produce, mtrl/rl/sampling_algs.py).  DESIGN.md section 18.
+ * mtsac_set_task_batch_sizes: sizes [T] with sizes[t] >= 0, sizes[t] <= capacity and sum == batch_per_task * T
+ * (else -22); NULL: back to the balanced sampler.  While set, the step's OWN device sampling -- mtsac_sample,
+ * mtsac_update(batch = NULL), mtsac_update_many -- draws, for t = 0 .. T-1 with sizes[t] > 0, what
+ * rng.integers(0, max(buffer_size, sizes[t]), size=sizes[t]) draws, on the one PCG64 stream (the buffered 32-bit
+ * half and every rejection carry over from task to task; a task of size 0 makes no call), and returns the rows
+ * task by task: row off[t] + j = store[idx_t[j]][t], off the exclusive prefix sums.  mtsac_sample's `indices`
+ * then has one entry per row ([batch_per_task * T], task-major).  Rewards are RAW on this path whatever
+ * normalize_rewards says: only the reference's int branch normalises.  mtsac_task_gradients and
+ * mtsac_network_metrics with batch == NULL keep sampling balanced, interleaved rows.
+ * -95 on a task-sharded engine (and from the step calls when collectives are attached afterwards) and while
+ * PCGrad, CAGrad or GradNorm is on; their setters return -95 while sizes are set.  The sizes live in device
+ * memory (counts, exclusive offsets, contiguous row lists) at fixed addresses: setting or clearing the mode drops
+ * a captured step graph, new sizes alone do not, and mtsac_enable_graph(1) works in this mode -- the replayed
+ * steps are bit-identical to eager ones.  The device noise of the plain step is drawn per row (it never shared
+ * draws across the tasks of a sample index), so row b of an uneven batch reads the stream balanced row b reads.
+ * mtsac_get_task_batch_sizes: the sizes in force (batch_per_task each when none are set); returns 1 when set,
+ * 0 when balanced.
+ * mtsac_set_task_loss_logging: on = 1 adds one launch to the plain step that reduces its per-row loss terms per
+ * task in a fixed order (no atomics); default off, the step then launches nothing new.  Switching drops a
+ * captured step graph.  mtsac_get_task_losses: out[0][t] = the mean over task t's rows and the ensemble of
+ * w (Q_e - y)^2, out[1][t] = the mean over its rows of w (alpha logpi - min_e Q_e), of the last plain step
+ * (any batch source); 0 for a task without rows; -22 when logging was never on. */
+int mtsac_set_task_batch_sizes(mtsac_engine* h, const int32_t* sizes /* [T] or NULL */);
+int mtsac_get_task_batch_sizes(mtsac_engine* h, int32_t* sizes /* [T] */);
+int mtsac_set_task_loss_logging(mtsac_engine* h, int32_t on);
+int mtsac_get_task_losses(mtsac_engine* h, float* out /* [2][T] */);
+
 /* one gradient step.  batch == NULL: sample from the device buffer.
  * eps_next / eps_cur ([B_local][A] N(0,1) noise for a' ~ pi(.|s') and a ~ pi(.|s));
  * both NULL: device counter-based normal stream. */

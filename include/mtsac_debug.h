@@ -264,7 +264,14 @@ int mtsac_debug_layout(int kind, const int* dims, const float* x, void* out, voi
  * high_or_size on the device (high = max(size, n)).  The jump table is pcg_jump_table's, as in the engines.
  * idx [n_alloc], n_alloc >= n: positions >= n must come back -1.  -22 for high >= 2^31. */
 int mtsac_debug_replay_indices(uint64_t* state, int mode, int64_t high_or_size, int n, int n_alloc, int32_t* idx);
-/* replay_gather (dims[0] = 0: store [cap][T_l][R] and idx [n], B = n T_l rows) or batch_scatter (dims[0] = 1: the
+/* replay_indices_tasks (per-task batch sizes): sizes [T], T <= 64, with *buf_size = size on the device; task t's
+ * sizes[t] draws of integers(0, max(size, sizes[t])) land at idx[off[t] ..), off the exclusive prefix sums.  idx
+ * [n_alloc], n_alloc >= sum(sizes) >= 1: positions past the sum must come back -1. */
+int mtsac_debug_replay_indices_tasks(uint64_t* state, int64_t size, int T, const int32_t* sizes, int n_alloc,
+                                     int32_t* idx);
+/* replay_gather (dims[0] = 0: store [cap][T_l][R] and idx [n], B = n T_l rows), replay_gather_tasks (dims[0] = 2:
+ * the task-major form, idx [B], dims [17 + T_l] with dims[17 + t] = the rows of task t, summing to B = n T_l;
+ * rmin / rmax must be NULL) or batch_scatter (dims[0] = 1: the
  * five user arrays of B = n rows, row b of local task b % T_l).  dims [17] = source, n, T_l, cap, obs_dim D,
  * act_dim A, T_glob, task_begin, ld_a, ld_c, plane mode (0 none, 1 split3, 2 split2h with *in_max), pa_ld, pc_ld,
  * pa_next, rows allocated per pa plane, rows allocated per pc / pcn / pcp plane, R.  rmin / rmax [T_l] (both or

@@ -124,6 +124,10 @@ SIGNATURES = {
     "mtsac_rng_set": (ctypes.c_int, [P, U64, U64, U64, U64, I32, U32]),
     "mtsac_rng_get": (ctypes.c_int, [P, PU64, PU64, PU64, PU64, PI32, PU32]),
     "mtsac_sample": (ctypes.c_int, [P, P, P, P, P, P, P]),
+    "mtsac_set_task_batch_sizes": (ctypes.c_int, [P, P]),
+    "mtsac_get_task_batch_sizes": (ctypes.c_int, [P, P]),
+    "mtsac_set_task_loss_logging": (ctypes.c_int, [P, I32]),
+    "mtsac_get_task_losses": (ctypes.c_int, [P, P]),
     "mtsac_update": (ctypes.c_int, [P, ctypes.POINTER(Batch), P, P]),
     "mtsac_update_many": (ctypes.c_int, [P, I32]),
     "mtsac_get_logs": (ctypes.c_int, [P, P]),
@@ -200,6 +204,7 @@ SIGNATURES = {
     "mtsac_debug_head_policy_noise": (ctypes.c_int, [ctypes.c_int] * 7 + [P] * 4 + [U64, U32, U64, ctypes.c_int] +
                                       [ctypes.c_float] * 2 + [P] * 7),
     "mtsac_debug_replay_indices": (ctypes.c_int, [P, ctypes.c_int, I64, ctypes.c_int, ctypes.c_int, P]),
+    "mtsac_debug_replay_indices_tasks": (ctypes.c_int, [P, I64, ctypes.c_int, P, ctypes.c_int, P]),
     "mtsac_debug_replay_gather": (ctypes.c_int, [P] * 10 + [ctypes.c_double] + [P] * 15),
     "mtsac_debug_task_rows": (ctypes.c_int, [ctypes.c_int] * 3 + [P] * 3),
     "mtsac_debug_pack_commit": (ctypes.c_int, [ctypes.c_int] * 4 + [I64] + [P] * 10),

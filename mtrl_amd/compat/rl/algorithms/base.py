@@ -8,6 +8,9 @@ buffer lives in the same engine as the networks, the sample + update pair runs a
 device call (``MTSACEngine.update_many(1)``): no host round trip per gradient step.
 At every evaluation the gradient-conflict metrics run on a balanced sample (``compute_weights``,
 base.py:279-288): ``config.batch_size`` rows, the reference's 128 per task in every target config.
+``TrainingConfig.sampler_type`` ("loss" / "adaptive"; the reference declares the field and never reads it):
+every ``update_weights_every`` gradient steps the per-task critic losses of the last step become new per-task
+batch sizes (``setup_task_sampler`` / ``task_sampler_step``; algorithms that cannot raise NotImplementedError).
 """
 
 from __future__ import annotations
@@ -61,6 +64,19 @@ class OffPolicyAlgorithm(Algorithm):
         """sample + update; overridden by engines that sample on the device."""
         return self.update(replay_buffer.sample(batch_size))
 
+    # ---- per-task batch-size sampler (TrainingConfig.sampler_type); overridden where the engine can
+    def setup_task_sampler(self, config) -> None:
+        if getattr(config, "sampler_type", None) is not None:
+            raise NotImplementedError(f"{type(self).__name__}: sampler_type needs per-task batch sizes in the "
+                                      "update engine; leave it None")
+
+    def task_sampler_step(self) -> LogDict:
+        """After every gradient step; the ``sampler/batch_size_task_{t}`` logs of a step that set new sizes."""
+        return {}
+
+    def task_sampler_restore(self) -> None:
+        """After a balanced ``replay_buffer.sample(int)`` (the evaluation metrics), which clears the sizes."""
+
     def train(self, config, envs, eval_envs, env_config, run_timestamp: str | None = None, seed: int = 1,
               track: bool = False, checkpoint_manager=None, checkpoint_metadata=None, buffer_checkpoint=None):
         T = self.num_tasks
@@ -77,6 +93,7 @@ class OffPolicyAlgorithm(Algorithm):
         if buffer_checkpoint is not None:
             replay_buffer.load_checkpoint(buffer_checkpoint)
         self._last_buffer = replay_buffer
+        self.setup_task_sampler(config)
         start_time = time.time()
         total_steps = 0
         if track:
@@ -108,8 +125,11 @@ class OffPolicyAlgorithm(Algorithm):
             if global_step > config.warmstart_steps:
                 for _ in range(getattr(config, "replay_ratio", 1)):
                     self, logs = self.update_from_buffer(replay_buffer, config.batch_size, want_logs=track)
+                    sampler_logs = self.task_sampler_step()
                     if track:
                         wandb.log(logs, step=total_steps)
+                        if sampler_logs:
+                            wandb.log(sampler_logs, step=total_steps)
                 if global_step % 10000 == 0:
                     sps = int((global_step - start_step) * envs.num_envs / (time.time() - start_time))
                     print("SPS:", sps)
@@ -130,6 +150,7 @@ class OffPolicyAlgorithm(Algorithm):
                         # the reference samples envs.num_envs * 128 rows; the engine's batch is
                         # config.batch_size, which is 128 per task in every target config
                         metrics_data = replay_buffer.sample(config.batch_size)
+                        self.task_sampler_restore()
                         self, update_logs = self.compute_weights(metrics_data)
                         if track:
                             wandb.log(update_logs, step=total_steps)

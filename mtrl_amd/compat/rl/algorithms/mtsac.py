@@ -29,6 +29,7 @@ from ...config.optim import CAGradConfig, GradNormConfig, OptimizerConfig, PCGra
 from ...config.rl import AlgorithmConfig
 from ...config.utils import Activation, Initializer, Optimizer
 from ..buffers import MultiTaskReplayBuffer
+from ..sampling_algs import make_sampler
 from .base import OffPolicyAlgorithm
 
 
@@ -214,6 +215,11 @@ class MTSAC(OffPolicyAlgorithm):
         # gradient-surgery step with that method's solve
         self.surgery: str | None = None
         self.shared_head = False  # the engine holds the Vanilla (shared-head) tree (initialize(shared_head=True))
+        # TrainingConfig.sampler_type: the sampler, its period in gradient steps, the steps so far, the sizes in
+        # force and every sizes log so far (setup_task_sampler)
+        self._sampler = None
+        self._sampler_every, self._sampler_steps, self._sampler_sizes = 1, 0, None
+        self.sampler_log_history: list[dict] = []
 
     pcgrad = property(lambda self: self.surgery == "pcgrad")
     cagrad = property(lambda self: self.surgery == "cagrad")
@@ -354,6 +360,48 @@ class MTSAC(OffPolicyAlgorithm):
             self.engine.update_many(1)  # device sampling + update, no host round trip
             return self, _DeviceLogs(self.engine, self.surgery)
         return super().update_from_buffer(replay_buffer, batch_size, want_logs)
+
+    # ------------------------------------------------------------------ per-task batch-size sampler
+    def setup_task_sampler(self, config) -> None:
+        """``sampler_type`` "loss" (Sampler) or "adaptive" (AdaptiveSampler) of mtrl/rl/sampling_algs.py.  The
+        reference declares ``sampler_type`` and ``update_weights_every`` and never reads them; this wiring is
+        ours: every ``update_weights_every`` gradient steps the last step's per-task critic losses become the
+        per-task batch sizes of the following device-sampled steps."""
+        kind = getattr(config, "sampler_type", None)
+        self._sampler, self._sampler_steps, self._sampler_sizes = None, 0, None
+        if kind is None:
+            return
+        sampler = make_sampler(kind, self.num_tasks)
+        if self.surgery:
+            raise NotImplementedError(
+                f"sampler_type={kind!r} with {_SURGERY[self.surgery][1]}: the gradient-surgery step reads "
+                "interleaved rows with the same count for every task (its per-task weight grads stride the batch "
+                "by T), so it cannot run on per-task batch sizes")
+        if self.engine.T_l != self.num_tasks:
+            raise NotImplementedError(
+                f"sampler_type={kind!r} on a task-sharded engine: the sizes are normalised over every task's loss "
+                "and the batch total is fixed over all tasks, so all tasks must live on one engine")
+        self._sampler = sampler
+        self._sampler_every = max(1, int(config.update_weights_every))
+        self.engine.set_task_loss_logging(True)
+
+    def task_sampler_step(self):
+        if self._sampler is None:
+            return {}
+        self._sampler_steps += 1
+        if self._sampler_steps % self._sampler_every:
+            return {}
+        losses = self.engine.task_losses()[0]  # the critic's
+        sizes = np.asarray(self._sampler.sample_batch_sizes(losses, self.engine.B), np.int64)
+        self.engine.set_task_batch_sizes(sizes)
+        self._sampler_sizes = sizes
+        logs = {f"sampler/batch_size_task_{t}": int(sizes[t]) for t in range(self.num_tasks)}
+        self.sampler_log_history.append(logs)
+        return logs
+
+    def task_sampler_restore(self) -> None:
+        if self._sampler_sizes is not None:
+            self.engine.set_task_batch_sizes(self._sampler_sizes)
 
     def compute_weights(self, data):
         """mtsac.py:870-1170: per-task gradient-conflict metrics at evaluation time (no update).

@@ -1,6 +1,10 @@
 """MultiTaskReplayBuffer (mtrl/rl/buffers.py:221-549) backed by the engine's
 device-resident buffer: same add / sample / checkpoint / load_checkpoint API, same
 index stream (numpy PCG64 reproduced on the device), same row layout (row = i*T + t).
+``sample`` takes the reference's two forms: an ``int`` (balanced, interleaved rows) or an array of per-task
+batch sizes (one ``integers`` call per non-empty task on the same stream, task-major rows, raw rewards;
+buffers.py:496-519).  ``single_task_sample`` is not restated: the reference's version indexes the sample
+axis with the task id.
 
 Return normalisation (``returns_normalization=True``, buffers.py:347-422) keeps the reference's
 per-episode bookkeeping here on the host (float64, the reward values as passed to ``add``); the
@@ -111,9 +115,22 @@ class MultiTaskReplayBuffer:
             if self._update_return_stats(raw_reward, term.astype(bool), trunc.astype(bool)):
                 self._push_denominator()
 
-    def sample(self, batch_size: int) -> ReplayBufferSamples:
-        assert batch_size % self.num_tasks == 0
-        assert batch_size // self.num_tasks == self.engine.config.batch_per_task
+    def sample(self, batch_size: int | np.ndarray) -> ReplayBufferSamples:
+        """buffers.py:494-549.  An ``int``: ``batch_size // T`` rows per task, interleaved (row = i*T + t),
+        rewards normalised as configured; per-task sizes left in the engine are cleared first.  An array of
+        per-task sizes (length T, summing to the engine's batch): task t draws its own ``batch_size[t]``
+        indices from the one stream and the rows come back task by task, rewards raw (buffers.py:496-519).
+        The sizes stay set in the engine, so the following device-sampled updates draw the same geometry."""
+        if isinstance(batch_size, (int, np.integer)):
+            assert batch_size % self.num_tasks == 0
+            assert batch_size // self.num_tasks == self.engine.config.batch_per_task
+            if self.engine.task_batch_sizes_set():
+                self.engine.set_task_batch_sizes(None)
+        else:
+            sizes = np.asarray(batch_size)
+            assert sizes.shape == (self.num_tasks,), "one batch size per task"
+            assert int(sizes.sum()) == self.engine.B, "per-task batch sizes must sum to the engine's batch"
+            self.engine.set_task_batch_sizes(sizes)
         _, (obs, act, nobs, done, rew) = self.engine.sample()
         return ReplayBufferSamples(obs, act, nobs, done, rew)
 

@@ -734,6 +734,41 @@ int mtsac_debug_replay_indices(uint64_t* state, int mode, int64_t high_or_size, 
   return 0;
 }
 
+int mtsac_debug_replay_indices_tasks(uint64_t* state, int64_t size, int T, const int32_t* sizes, int n_alloc,
+                                     int32_t* idx) {
+  if (!state || !idx || !sizes || T < 1 || T > 64 || size < 0 || size >= (1LL << 31) || n_alloc < 1 ||
+      n_alloc > (1 << 24) || (state[4] & ~1ull) || state[5] > 0xFFFFFFFFull)
+    return -22;
+  std::vector<int> offs(T + 1, 0);
+  for (int t = 0; t < T; ++t) {
+    if (sizes[t] < 0 || sizes[t] > n_alloc) return -22;
+    offs[t + 1] = offs[t] + sizes[t];
+    if (offs[t + 1] > n_alloc) return -22;
+  }
+  const int total = offs[T];
+  if (total < 1) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  unsigned long long jt[65 * 4];
+  pcg_jump_table(jt);
+  PcgDev s{state[0], state[1], state[2], state[3], (int)state[4], (unsigned)state[5]};
+  const long long sz = size;
+  Guarded g;
+  const unsigned long long* d_jump = g.in(jt, (size_t)65 * 4);
+  const long long* d_size = g.in(&sz, 1);
+  const int* d_sizes = g.in(sizes, (size_t)T);
+  const int* d_offs = g.in(offs.data(), (size_t)T + 1);
+  PcgDev* d_rng = guarded_inout(g, &s, 1, "rng");
+  int* d_idx = g.out<int>((size_t)n_alloc, "idx");
+  if (!g.ok) return -12;
+  replay_indices_tasks(d_rng, d_jump, d_size, d_sizes, d_offs, T, total, d_idx, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("replay_indices_tasks")) || (rc = g.check())) return rc;
+  if (!g.back(&s, d_rng, 1) || !g.back(idx, d_idx, (size_t)n_alloc)) return -5;
+  state[0] = s.state_hi; state[1] = s.state_lo; state[2] = s.inc_hi; state[3] = s.inc_lo;
+  state[4] = (uint64_t)(unsigned)s.has_uint32; state[5] = s.uinteger;
+  return 0;
+}
+
 int mtsac_debug_replay_gather(const int* dims, const float* store, const int32_t* idx, const float* u_obs,
                               const float* u_act, const float* u_nobs, const float* u_done, const float* u_rew,
                               const double* rmin, const double* rmax, double norm_eps, const float* in_max, float* xa,
@@ -744,14 +779,23 @@ int mtsac_debug_replay_gather(const int* dims, const float* store, const int32_t
   const int src = dims[0], n = dims[1], T_l = dims[2], cap = dims[3], D = dims[4], A = dims[5], T_glob = dims[6],
             task_begin = dims[7], ld_a = dims[8], ld_c = dims[9], pm = dims[10], pa_ld = dims[11], pc_ld = dims[12],
             pa_next = dims[13], pa_rows = dims[14], pc_rows = dims[15], R = dims[16];
-  if ((src != 0 && src != 1) || n < 1 || T_l < 1 || T_l > 64 || D < 1 || A < 1 || A > 64 || T_glob < 1 || T_glob > D ||
+  if ((src != 0 && src != 1 && src != 2) || n < 1 || T_l < 1 || T_l > 64 || D < 1 || A < 1 || A > 64 || T_glob < 1 || T_glob > D ||
       task_begin < 0 || ld_a < D || ld_c < A + D || R < 2 * D + A + 2 || pm < 0 || pm > 2 || (long long)n * T_l > (1 << 20) ||
       !xa || !xa_next || !xc || !xc_next || !xc_pi || !rew || !done || !task || !err || (rmin == nullptr) != (rmax == nullptr))
     return -22;
-  const int B = src == 0 ? n * T_l : n;
-  if (src == 0) {
+  const int B = src != 1 ? n * T_l : n;
+  std::vector<int> offs(T_l + 1, 0);
+  if (src == 2) {  // task-major: dims[17 + t] rows of task t, one index per row; no reward normalisation
+    if (rmin) return -22;
+    for (int t = 0; t < T_l; ++t) {
+      if (dims[17 + t] < 0 || dims[17 + t] > B) return -22;
+      offs[t + 1] = offs[t] + dims[17 + t];
+    }
+    if (offs[T_l] != B) return -22;
+  }
+  if (src != 1) {
     if (!store || !idx || cap < 1 || (long long)cap * T_l * R >= (1LL << 27)) return -22;
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; i < (src == 2 ? B : n); ++i)
       if (idx[i] < 0 || idx[i] >= cap) return -22;
   } else if (!u_obs || !u_act || !u_nobs || !u_done || !u_rew) {
     return -22;
@@ -762,8 +806,9 @@ int mtsac_debug_replay_gather(const int* dims, const float* store, const int32_t
   if (hipSetDevice(0) != hipSuccess) return -5;
   Guarded g;
   GatherParams p{};
-  p.store = src == 0 ? g.in(store, (size_t)cap * T_l * R) : nullptr;
-  p.idx = src == 0 ? g.in(idx, (size_t)n) : nullptr;
+  p.store = src != 1 ? g.in(store, (size_t)cap * T_l * R) : nullptr;
+  p.idx = src != 1 ? g.in(idx, (size_t)(src == 2 ? B : n)) : nullptr;
+  p.offs = src == 2 ? g.in(offs.data(), (size_t)T_l + 1) : nullptr;
   p.n = n; p.T_l = T_l; p.R = R; p.obs_dim = D; p.act_dim = A; p.T_glob = T_glob; p.task_begin = task_begin;
   p.ld_a = ld_a; p.ld_c = ld_c;
   p.xa = g.out<float>((size_t)B * ld_a, "xa");
@@ -801,6 +846,7 @@ int mtsac_debug_replay_gather(const int* dims, const float* store, const int32_t
   }
   if (!g.ok) return -12;
   if (src == 0) replay_gather(p, nullptr);
+  else if (src == 2) replay_gather_tasks(p, nullptr);
   else batch_scatter(p, d_o, d_a, d_no, d_d, d_r, B, nullptr);
   int rc = 0;
   if ((rc = sync_rc("gather")) || (rc = g.check())) return rc;

@@ -257,6 +257,17 @@ struct mtsac_engine {
   // Device-sampled batches are interleaved (row i*T_l + t, buffers.py:548), so their per-task row
   // lists are fixed: counts = n, rows[t][i] = i*T_l + t, uploaded once (no task_rows launch per step)
   int *s_counts = nullptr, *s_rows = nullptr;
+  // Per-task batch sizes (mtsac_set_task_batch_sizes; MultiTaskReplayBuffer.sample with an array,
+  // buffers.py:496-519): the step's own device sampling draws ts_counts[t] indices per task and gathers the rows
+  // task-major.  Device-resident -- the counts, their exclusive offsets [T_l + 1], the contiguous row lists
+  // [T_l][B] (the stride of a user batch's lists) and one index per row -- at fixed addresses, so new sizes
+  // need no new buffers; the head grids are sized for a task of up to B rows.  Allocated at the first use.
+  bool uneven = false;
+  std::vector<int> h_sizes;
+  int *ts_counts = nullptr, *ts_offs = nullptr, *ts_rows = nullptr, *ts_idx = nullptr;
+  // per-task mean loss terms of the plain step (mtsac_set_task_loss_logging): [2][T_l], 0 critic, 1 actor
+  bool tl_on = false;
+  float* tl_out = nullptr;
   hipEvent_t ev_ap[2] = {}, ev_tail[2] = {};  // step k's s_ap / last segment, by step parity
   bool have_prev = false;                      // a pipelined step k is in flight (its events valid)
   // Cross-step pipelining of eager update_many: -1 auto (on when the trunk gradients go through a
@@ -1682,9 +1693,21 @@ struct mtsac_engine {
     return ch_loss(c, CH_ACTOR, chp, inv_norm, dq_rec);
   }
   // the batch (a replay sample, or the uploaded user batch) into the input buffers; row lists: the caller's
-  void load_batch(bool device_batch) {
+  // the per-task-sizes sample: the index stream task by task, then the task-major gather with raw rewards
+  // (only the reference's int branch normalises, buffers.py:531-538)
+  void sample_tasks(GatherParams gp, hipStream_t s) {
+    gp.idx = ts_idx;
+    gp.offs = ts_offs;
+    gp.rmin = gp.rmax = nullptr;
+    replay_indices_tasks(rng, jump, buf_size, ts_counts, ts_offs, T_l, B, ts_idx, s);
+    replay_gather_tasks(gp, s);
+  }
+  // task_sizes: the step's own sampling under mtsac_set_task_batch_sizes (the eval passes stay balanced)
+  void load_batch(bool device_batch, bool task_sizes = false) {
     GatherParams gp = gather_params();
-    if (device_batch) {
+    if (device_batch && task_sizes) {
+      sample_tasks(gp, cur);
+    } else if (device_batch) {
       replay_indices(rng, jump, buf_size, n, idx, cur);
       replay_gather(gp, cur);
     } else {
@@ -1703,8 +1726,9 @@ struct mtsac_engine {
     // lanes: step k's tail is on lanes 1, 3, 4 and the overlapped segments start on lane 0.
     const bool p2 = one_stream;
     if (overlap) use_inset(inset_cur ^ 1);
-    counts = device_batch ? s_counts : inset[inset_cur].counts;
-    rows = device_batch ? s_rows : inset[inset_cur].rows;
+    const bool ts = device_batch && uneven;  // per-task sizes: contiguous row lists, fixed like s_rows
+    counts = ts ? ts_counts : device_batch ? s_counts : inset[inset_cur].counts;
+    rows = ts ? ts_rows : device_batch ? s_rows : inset[inset_cur].rows;
     if (!ev_rotate) ev_next = 0;
     segs.clear();
     actor.fin_sink.n = critic.fin_sink.n = 0;  // (a step cut short never leaves deferred finishes behind)
@@ -1712,8 +1736,8 @@ struct mtsac_engine {
     zstep[1] = zero_ok(critic);
     PolicyParams pp;
     CriticHeadParams ch;
-    // replay batches hold exactly n rows per task
-    head_base(pp, ch, device_batch ? n : Bl, critic.arows * critic.xld, (int)critic.xld);
+    // balanced replay batches hold exactly n rows per task; a task of a user batch or of per-task sizes up to Bl
+    head_base(pp, ch, device_batch && !ts ? n : Bl, critic.arows * critic.xld, (int)critic.xld);
 
     if (overlap) {  // the gather and critic(s, a) reuse buffers step k's actor-loss pass reads
       hipStream_t w = p2 ? s2 : st;
@@ -1723,7 +1747,7 @@ struct mtsac_engine {
     }
     pf_issue = overlap && p2;
     const int s_in = seg({}, 0, [&] {
-      load_batch(device_batch);
+      load_batch(device_batch, ts);
       if (!device_batch) task_rows(task, Bl, T_l, counts, rows, Bl, cur);  // a user batch: lists from its task ids
       if (cfg.use_task_weights) row_alpha(task, cfg.task_begin, log_alpha, T_g, Bl, 1, row_c, tw, cur);
     });
@@ -1850,6 +1874,8 @@ struct mtsac_engine {
       allreduce(pn + 2, 2);
       StepFinish f = finish_params(al);
       step_finish(f, cur);
+      // per-task means of the per-row loss terms (off by default: nothing is launched)
+      if (tl_on) task_losses_rows(row_a, row_c, counts, rows, Bl, T_l, critic.E, tl_out, cur);
     });
     if (pipelined) (void)hipEventRecord(ev_tail[step_par], segs[s_tail].lane);
     if (!build && (join || !pipelined)) {  // eager: the main stream waits for every lane
@@ -2351,6 +2377,9 @@ struct mtsac_engine {
     if (sg.kind && sg.kind != kind)
       return fail(-16, std::string(names[sg.kind]) + " is on (" + undo[sg.kind] + "(0) first)");
     if (T_l != T_g || sharded()) return fail(-95, std::string(name) + " needs every task on one engine (unsharded)");
+    if (uneven)
+      return fail(-95, std::string(name) + " with per-task batch sizes: the split passes read interleaved rows "
+                                           "(mtsac_set_task_batch_sizes(NULL) first)");
     if (cfg.use_task_weights)
       return fail(-95, std::string(name) +
                            " with use_task_weights: the reference's split losses multiply by the unsplit weights");
@@ -3317,17 +3346,22 @@ int mtsac_rng_get(mtsac_engine* h, uint64_t* shi, uint64_t* slo, uint64_t* ihi, 
 int mtsac_sample(mtsac_engine* h, int64_t* indices, float* obs, float* actions, float* next_obs, float* dones,
                  float* rewards) {
   if (!h) return fail(-22, "null engine");
-  replay_indices(h->rng, h->jump, h->buf_size, h->n, h->idx, h->st);
   GatherParams gp = h->gather_params();
-  replay_gather(gp, h->st);
+  if (h->uneven) {
+    h->sample_tasks(gp, h->st);
+  } else {
+    replay_indices(h->rng, h->jump, h->buf_size, h->n, h->idx, h->st);
+    replay_gather(gp, h->st);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->st));
   const int B = h->B, D = h->D, A = h->A;
-  if (indices) {
-    std::vector<int> tmp(h->n);
-    HIP_TRY(hipMemcpy(tmp.data(), h->idx, sizeof(int) * h->n, hipMemcpyDeviceToHost));
+  if (indices) {  // n of them, or with per-task sizes one per row (task-major)
+    const int ni = h->uneven ? B : h->n;
+    std::vector<int> tmp(ni);
+    HIP_TRY(hipMemcpy(tmp.data(), h->uneven ? h->ts_idx : h->idx, sizeof(int) * ni, hipMemcpyDeviceToHost));
     std::vector<int64_t> wide(tmp.begin(), tmp.end());
-    HIP_TRY(hipMemcpy(indices, wide.data(), sizeof(int64_t) * h->n, hipMemcpyDefault));
+    HIP_TRY(hipMemcpy(indices, wide.data(), sizeof(int64_t) * ni, hipMemcpyDefault));
   }
   if (obs) HIP_TRY(hipMemcpy2D(obs, sizeof(float) * D, h->xa, sizeof(float) * h->ld_a, sizeof(float) * D, B,
                                hipMemcpyDefault));
@@ -3340,10 +3374,81 @@ int mtsac_sample(mtsac_engine* h, int64_t* indices, float* obs, float* actions, 
   return h->check_err();
 }
 
+// ---------------------------------------------------------------- per-task batch sizes, per-task losses
+int mtsac_set_task_batch_sizes(mtsac_engine* h, const int32_t* sizes) {
+  if (!h) return fail(-22, "null engine");
+  if (!sizes) {
+    if (!h->uneven) return 0;
+    HIP_TRY(hipStreamSynchronize(h->st));
+    h->uneven = false;
+    h->drop_graph();  // the captured step holds the other sampler and head grids
+    return 0;
+  }
+  if (h->T_l != h->T_g || h->sharded())
+    return fail(-95, "per-task batch sizes need every task on one engine (unsharded)");
+  if (h->sg.kind) return fail(-95, "per-task batch sizes with PCGrad / CAGrad / GradNorm on: the split passes read interleaved rows");
+  const int T = h->T_l, B = h->B;
+  long long sum = 0;
+  for (int t = 0; t < T; ++t) {
+    if (sizes[t] < 0) return fail(-22, "task batch sizes must be >= 0");
+    if (sizes[t] > h->cfg.capacity) return fail(-22, "a task's batch size exceeds the buffer's slots per task");
+    sum += sizes[t];
+  }
+  if (sum != B) return fail(-22, "task batch sizes must sum to batch_per_task * num_tasks (" + std::to_string(B) + ")");
+  if (!h->ts_counts) {
+    int rc = 0;
+    if ((rc = h->alloc(&h->ts_counts, T)) || (rc = h->alloc(&h->ts_offs, T + 1)) ||
+        (rc = h->alloc(&h->ts_rows, (size_t)T * B)) || (rc = h->alloc(&h->ts_idx, B)))
+      return rc;
+    HIP_TRY(hipDeviceSynchronize());  // alloc()'s null-stream zero fills
+  }
+  std::vector<int> offs(T + 1, 0), rows((size_t)T * B, 0);
+  for (int t = 0; t < T; ++t) {
+    offs[t + 1] = offs[t] + sizes[t];
+    for (int j = 0; j < sizes[t]; ++j) rows[(size_t)t * B + j] = offs[t] + j;
+  }
+  HIP_TRY(hipStreamSynchronize(h->st));  // steps in flight read the old sizes
+  HIP_TRY(hipMemcpy(h->ts_counts, sizes, sizeof(int) * T, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->ts_offs, offs.data(), sizeof(int) * (T + 1), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->ts_rows, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice));
+  h->h_sizes.assign(sizes, sizes + T);
+  if (!h->uneven) h->drop_graph();  // new sizes alone: the captured step reads them from the device
+  h->uneven = true;
+  return 0;
+}
+
+int mtsac_get_task_batch_sizes(mtsac_engine* h, int32_t* sizes) {
+  if (!h || !sizes) return fail(-22, "null argument");
+  for (int t = 0; t < h->T_l; ++t) sizes[t] = h->uneven ? h->h_sizes[t] : h->n;
+  return h->uneven ? 1 : 0;
+}
+
+int mtsac_set_task_loss_logging(mtsac_engine* h, int32_t on) {
+  if (!h) return fail(-22, "null engine");
+  if ((on != 0) == h->tl_on) return 0;
+  if (on && !h->tl_out) {
+    if (int rc = h->alloc(&h->tl_out, 2 * (size_t)h->T_l)) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+  }
+  HIP_TRY(hipStreamSynchronize(h->st));
+  h->tl_on = on != 0;
+  h->drop_graph();  // the captured step has, or lacks, the reduction
+  return 0;
+}
+
+int mtsac_get_task_losses(mtsac_engine* h, float* out) {
+  if (!h || !out) return fail(-22, "null argument");
+  if (!h->tl_out) return fail(-22, "per-task loss logging was never on (mtsac_set_task_loss_logging)");
+  HIP_TRY(hipMemcpyAsync(out, h->tl_out, sizeof(float) * 2 * h->T_l, hipMemcpyDefault, h->st));
+  HIP_TRY(hipStreamSynchronize(h->st));
+  return 0;
+}
+
 // ---------------------------------------------------------------- update
 int mtsac_update(mtsac_engine* h, const mtsac_batch* b, const float* eps_next, const float* eps_cur) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
+  if (!b && h->uneven && h->sharded()) return fail(-95, "per-task batch sizes need every task on one engine (unsharded)");
   if (int rc = h->upload(b, eps_next, eps_cur)) return rc;
   h->tl_next = 0;
   if (h->sg.kind) {
@@ -3844,6 +3949,7 @@ int mtsac_update_many(mtsac_engine* h, int32_t steps) {
   if (!h) return fail(-22, "null engine");
   if (int rc = h->geo_guard()) return rc;
   if (steps <= 0) return 0;
+  if (h->uneven && h->sharded()) return fail(-95, "per-task batch sizes need every task on one engine (unsharded)");
   if (h->sg.kind) {  // eager, one stream, no overlap between steps; PCGrad's task orders are drawn on the device
     if (h->sharded()) return fail(-95, "PCGrad / CAGrad / GradNorm needs every task on one engine (unsharded)");
     h->tl_next = 0;

@@ -57,6 +57,21 @@ __global__ __launch_bounds__(64) void task_losses_kernel(const float* __restrict
   out[t] = (float)(s * inv);
 }
 
+__global__ __launch_bounds__(64) void task_losses_rows_kernel(const float* __restrict__ row_critic,
+                                                              const float* __restrict__ row_actor,
+                                                              const int* __restrict__ counts,
+                                                              const int* __restrict__ rows, int max_rows, int T, int E,
+                                                              float* __restrict__ out) {
+  const int t = blockIdx.x, w = blockIdx.y, lane = threadIdx.x;
+  const float* row = w == 0 ? row_critic : row_actor;
+  const int n = min(counts[t], max_rows);
+  const int* list = rows + (long long)t * max_rows;
+  double s = 0.0;
+  for (int j = lane; j < n; j += 64) s += (double)row[list[j]];
+  s = wave_sum(s);
+  if (lane == 0) out[w * T + t] = n > 0 ? (float)(s / ((w == 0 ? (double)E : 1.0) * (double)n)) : 0.f;
+}
+
 __global__ __launch_bounds__(64) void gradnorm_solve_kernel(GradnormSolve s) {
 #pragma clang fp contract(off)
   const int i = threadIdx.x, T = s.T;
@@ -123,6 +138,12 @@ __global__ __launch_bounds__(64) void gradnorm_solve_kernel(GradnormSolve s) {
 
 void task_losses(const float* row, int T, int n, double inv, float* out, hipStream_t st) {
   hipLaunchKernelGGL(task_losses_kernel, dim3(1), dim3(64), 0, st, row, T, n, inv, out);
+}
+
+void task_losses_rows(const float* row_critic, const float* row_actor, const int* counts, const int* rows,
+                      int max_rows, int T, int E, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(task_losses_rows_kernel, dim3(T, 2), dim3(64), 0, st, row_critic, row_actor, counts, rows,
+                     max_rows, T, E, out);
 }
 
 void gradnorm_solve(const GradnormSolve& s, hipStream_t st) {

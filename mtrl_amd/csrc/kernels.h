@@ -239,9 +239,15 @@ void replay_indices(PcgDev* rng, const unsigned long long* jump /*65 x (A_hi,A_l
 void replay_indices_high(PcgDev* rng, const unsigned long long* jump, long long high, int n, int* idx_out,
                          hipStream_t st);
 
+// per-task batch sizes: sizes[t] draws of integers(0, max(size, sizes[t])) for every task with sizes[t] > 0, in
+// task order on the one stream, into idx_out[offs[t] ..); total = idx_out's length (sum of the sizes)
+void replay_indices_tasks(PcgDev* rng, const unsigned long long* jump, const long long* buf_size, const int* sizes,
+                          const int* offs, int T, int total, int* idx_out, hipStream_t st);
+
 struct GatherParams {
   const float* store;   // [cap][T_l][R] transition records
-  const int* idx;       // [n]
+  const int* idx;       // [n]; replay_gather_tasks: [n * T_l], one per row
+  const int* offs;      // replay_gather_tasks: [T_l + 1] exclusive row offsets of the tasks
   int n, T_l, R, obs_dim, act_dim, T_glob, task_begin;
   int ld_a, ld_c;       // padded widths of actor / critic inputs
   float* xa;            // [B][ld_a]  obs
@@ -271,6 +277,9 @@ struct GatherParams {
   const float* in_max;
 };
 void replay_gather(const GatherParams& p, hipStream_t st);
+// the task-major form: row offs[t] + j = store[idx[offs[t] + j]][t], task[row] = t (the caller leaves rmin null:
+// the reference's array branch returns raw rewards)
+void replay_gather_tasks(const GatherParams& p, hipStream_t st);
 // a user batch (ReplayBufferSamples layout) into the same input buffers
 void batch_scatter(const GatherParams& p, const float* obs, const float* act, const float* nobs,
                    const float* done, const float* rew, int B, hipStream_t st);
@@ -733,6 +742,11 @@ struct GradnormSolve {
                            // pre-surgery norm, where pcgrad_logs reads it)
 };
 void task_losses(const float* row, int T, int n, double inv, float* out, hipStream_t st);
+// The same over per-task row lists (counts [T], rows [T][max_rows]), for the plain step: out[0][t] = the mean over
+// task t's rows of row_critic / E, out[1][t] the mean of row_actor; a task without rows gives 0.  One wavefront
+// per (network, task): lane l adds rows l, l + 64, ... in order in fp64, then the fixed shuffle tree.
+void task_losses_rows(const float* row_critic, const float* row_actor, const int* counts, const int* rows,
+                      int max_rows, int T, int E, float* out, hipStream_t st);
 void gradnorm_solve(const GradnormSolve& s, hipStream_t st);
 
 // ------------------------------------------------------------------ network health metrics (netmetrics.hip;

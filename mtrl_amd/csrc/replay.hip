@@ -22,6 +22,86 @@ namespace mtsac {
 // draws are "the accepted candidates, in stream order": each lane of ONE wave
 // advances the LCG by (lane + 1) steps with a precomputed jump (A_j, C_j) and
 // offers two candidates (lo, hi); a ballot prefix count places the accepted ones.
+// The stream lives in registers while a kernel draws (wave-uniform between draws), so several draws in one
+// launch continue one another exactly as consecutive integers() calls do.
+struct PcgRegs {
+  u128 s;
+  int has32;
+  unsigned int uinteger;
+};
+struct WaveJump {  // lane's jump of (lane + 1) LCG steps, the wave's of 64, the lanes below
+  u128 Aj, Cj, A64, C64;
+  unsigned long long below;
+};
+__device__ inline WaveJump wave_jump(const unsigned long long* __restrict__ jump, int lane) {
+  WaveJump j;
+  j.Aj = {jump[4 * (lane + 1) + 0], jump[4 * (lane + 1) + 1]};
+  j.Cj = {jump[4 * (lane + 1) + 2], jump[4 * (lane + 1) + 3]};
+  j.A64 = {jump[4 * 64 + 0], jump[4 * 64 + 1]};
+  j.C64 = {jump[4 * 64 + 2], jump[4 * 64 + 3]};
+  j.below = (lane == 0) ? 0ull : ((~0ull) >> (64 - lane));
+  return j;
+}
+__device__ inline unsigned long long shfl_u64(unsigned long long v, int src) {
+  const unsigned int lo = __shfl((unsigned int)v, src), hi = __shfl((unsigned int)(v >> 32), src);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ inline PcgRegs pcg_load(const PcgDev* rng) {
+  return PcgRegs{{rng->state_hi, rng->state_lo}, rng->has_uint32, rng->uinteger};
+}
+__device__ inline void pcg_store(PcgDev* rng, const PcgRegs& g) {
+  rng->state_hi = g.s.hi;
+  rng->state_lo = g.s.lo;
+  rng->has_uint32 = g.has32;
+  rng->uinteger = g.uinteger;
+}
+
+// n >= 1 draws of integers(0, high), 2 <= high < 2**31, into idx[0 .. n); one wave, g uniform on entry and exit
+__device__ inline void draw_bounded(PcgRegs& g, const u128 inc, const WaveJump& wj, unsigned int hi32, int n,
+                                    int* __restrict__ idx, int lane) {
+  const unsigned int threshold = (0xFFFFFFFFu - (hi32 - 1u)) % hi32;
+  int produced = 0;
+  if (g.has32) {  // the buffered high half is the first candidate
+    g.has32 = 0;
+    const unsigned long long m = (unsigned long long)g.uinteger * hi32;
+    if ((unsigned int)m >= threshold) {
+      if (lane == 0) idx[0] = (int)(m >> 32);
+      produced = 1;
+    }
+  }
+  if (produced >= n) return;
+  u128 s = g.s;
+  while (true) {
+    const u128 sj = add128(mul128(wj.Aj, s), mul128(wj.Cj, inc));  // state after lane+1 steps
+    const unsigned long long o = pcg64_output(sj);
+    const unsigned int c_lo = (unsigned int)o, c_hi = (unsigned int)(o >> 32);
+    const unsigned long long m_lo = (unsigned long long)c_lo * hi32;
+    const unsigned long long m_hi = (unsigned long long)c_hi * hi32;
+    const bool a_lo = (unsigned int)m_lo >= threshold;
+    const bool a_hi = (unsigned int)m_hi >= threshold;
+    const unsigned long long B_lo = __ballot(a_lo);
+    const unsigned long long B_hi = __ballot(a_hi);
+    const int before = __popcll(B_lo & wj.below) + __popcll(B_hi & wj.below);
+    const int pos_lo = produced + before;
+    const int pos_hi = pos_lo + (a_lo ? 1 : 0);
+    if (a_lo && pos_lo < n) idx[pos_lo] = (int)(m_lo >> 32);
+    if (a_hi && pos_hi < n) idx[pos_hi] = (int)(m_hi >> 32);
+    const int total = __popcll(B_lo) + __popcll(B_hi);
+    if (produced + total >= n) {
+      // the candidate that yielded draw n-1 fixes the final generator state: its lane hands it to the wave
+      const bool end_lo = a_lo && pos_lo == n - 1, end_hi = a_hi && pos_hi == n - 1;
+      const int src = __ffsll((long long)__ballot(end_lo || end_hi)) - 1;
+      g.s.hi = shfl_u64(sj.hi, src);
+      g.s.lo = shfl_u64(sj.lo, src);
+      g.has32 = __shfl(end_lo ? 1 : 0, src);  // the low half ended the call: its high half stays buffered
+      g.uinteger = __shfl(c_hi, src);         // (pcg64_next32 leaves a consumed high word in place)
+      return;
+    }
+    produced += total;
+    s = add128(mul128(wj.A64, s), mul128(wj.C64, inc));
+  }
+}
+
 __global__ __launch_bounds__(64) void replay_indices_kernel(PcgDev* rng, const unsigned long long* __restrict__ jump,
                                                             const long long* __restrict__ buf_size, int n,
                                                             int* __restrict__ idx, long long exact_high) {
@@ -33,68 +113,38 @@ __global__ __launch_bounds__(64) void replay_indices_kernel(PcgDev* rng, const u
     for (int i = lane; i < n; i += 64) idx[i] = 0;  // rng == 0: no stream consumption
     return;
   }
-  const unsigned int hi32 = (unsigned int)high;  // high < 2**31 (checked at create)
-  const unsigned int threshold = (0xFFFFFFFFu - (hi32 - 1u)) % hi32;
-
-  u128 s = {rng->state_hi, rng->state_lo};
+  PcgRegs g = pcg_load(rng);
   const u128 inc = {rng->inc_hi, rng->inc_lo};
-  int has32 = rng->has_uint32;
-  const unsigned int buffered = rng->uinteger;
-  int produced = 0;
+  draw_bounded(g, inc, wave_jump(jump, lane), (unsigned int)high /* < 2**31, checked at create */, n, idx, lane);
+  if (lane == 0) pcg_store(rng, g);
+}
 
-  if (has32) {  // the buffered high half is the first candidate
-    has32 = 0;
-    const unsigned long long m = (unsigned long long)buffered * hi32;
-    if ((unsigned int)m >= threshold) {
-      if (lane == 0) idx[0] = (int)(m >> 32);
-      produced = 1;
+// Per-task batch sizes (buffers.py:496-519): for every task t with sizes[t] > 0, in task order, one
+// integers(0, max(size, sizes[t]), size=sizes[t]) call into idx[offs[t] ..) -- ONE stream: the buffered half and
+// every rejection carry from a task's call into the next.  A task of size 0 makes no call.  total: idx's length.
+__global__ __launch_bounds__(64) void replay_indices_tasks_kernel(PcgDev* rng,
+                                                                  const unsigned long long* __restrict__ jump,
+                                                                  const long long* __restrict__ buf_size,
+                                                                  const int* __restrict__ sizes,
+                                                                  const int* __restrict__ offs, int T, int total,
+                                                                  int* __restrict__ idx) {
+  const int lane = threadIdx.x;
+  const long long size = *buf_size;
+  PcgRegs g = pcg_load(rng);
+  const u128 inc = {rng->inc_hi, rng->inc_lo};
+  const WaveJump wj = wave_jump(jump, lane);
+  for (int t = 0; t < T; ++t) {
+    const int n = sizes[t], off = offs[t];
+    if (n <= 0) continue;
+    if (off < 0 || n > total - off) break;  // never past idx (the host validates the sizes it uploads)
+    const long long high = size > n ? size : (long long)n;
+    if (high <= 1) {
+      if (lane == 0) idx[off] = 0;  // n == 1: integers(0, 1) consumes nothing
+      continue;
     }
+    draw_bounded(g, inc, wj, (unsigned int)high, n, idx + off, lane);
   }
-  if (produced >= n) {
-    if (lane == 0) rng->has_uint32 = 0;
-    return;
-  }
-  const u128 Aj = {jump[4 * (lane + 1) + 0], jump[4 * (lane + 1) + 1]};
-  const u128 Cj = {jump[4 * (lane + 1) + 2], jump[4 * (lane + 1) + 3]};
-  const u128 A64 = {jump[4 * 64 + 0], jump[4 * 64 + 1]};
-  const u128 C64 = {jump[4 * 64 + 2], jump[4 * 64 + 3]};
-  const unsigned long long below = (lane == 0) ? 0ull : ((~0ull) >> (64 - lane));
-
-  while (true) {
-    const u128 sj = add128(mul128(Aj, s), mul128(Cj, inc));  // state after lane+1 steps
-    const unsigned long long o = pcg64_output(sj);
-    const unsigned int c_lo = (unsigned int)o, c_hi = (unsigned int)(o >> 32);
-    const unsigned long long m_lo = (unsigned long long)c_lo * hi32;
-    const unsigned long long m_hi = (unsigned long long)c_hi * hi32;
-    const bool a_lo = (unsigned int)m_lo >= threshold;
-    const bool a_hi = (unsigned int)m_hi >= threshold;
-    const unsigned long long B_lo = __ballot(a_lo);
-    const unsigned long long B_hi = __ballot(a_hi);
-    const int before = __popcll(B_lo & below) + __popcll(B_hi & below);
-    const int pos_lo = produced + before;
-    const int pos_hi = pos_lo + (a_lo ? 1 : 0);
-    if (a_lo && pos_lo < n) idx[pos_lo] = (int)(m_lo >> 32);
-    if (a_hi && pos_hi < n) idx[pos_hi] = (int)(m_hi >> 32);
-    const int total = __popcll(B_lo) + __popcll(B_hi);
-    if (produced + total >= n) {
-      // the candidate that yielded draw n-1 fixes the final generator state
-      if (a_lo && pos_lo == n - 1) {
-        rng->state_hi = sj.hi;
-        rng->state_lo = sj.lo;
-        rng->has_uint32 = 1;
-        rng->uinteger = c_hi;
-      } else if (a_hi && pos_hi == n - 1) {
-        rng->state_hi = sj.hi;
-        rng->state_lo = sj.lo;
-        rng->has_uint32 = 0;
-        rng->uinteger = c_hi;  // pcg64_next32 leaves the consumed high word in place
-      }
-      return;
-    }
-    produced += total;
-    s = add128(mul128(A64, s), mul128(C64, inc));
-    (void)has32;
-  }
+  if (lane == 0) pcg_store(rng, g);
 }
 
 void replay_indices(PcgDev* rng, const unsigned long long* jump, const long long* buf_size, int n, int* idx_out,
@@ -105,6 +155,12 @@ void replay_indices(PcgDev* rng, const unsigned long long* jump, const long long
 void replay_indices_high(PcgDev* rng, const unsigned long long* jump, long long high, int n, int* idx_out,
                          hipStream_t st) {
   hipLaunchKernelGGL(replay_indices_kernel, dim3(1), dim3(64), 0, st, rng, jump, nullptr, n, idx_out, high);
+}
+
+void replay_indices_tasks(PcgDev* rng, const unsigned long long* jump, const long long* buf_size, const int* sizes,
+                          const int* offs, int T, int total, int* idx_out, hipStream_t st) {
+  hipLaunchKernelGGL(replay_indices_tasks_kernel, dim3(1), dim3(64), 0, st, rng, jump, buf_size, sizes, offs, T, total,
+                     idx_out);
 }
 
 // ------------------------------------------------------------------ gather
@@ -124,9 +180,11 @@ __device__ inline int wave_min_i(int v) {
   return v;
 }
 
-// One wave per output row.  SRC_STORE: rows come from the device buffer through idx
-// (row b = i * T_l + t, buffers.py:541-548); otherwise from a user batch.
-template <bool SRC_STORE>
+// One wave per output row.  SRC_INTERLEAVED: rows come from the device buffer through idx
+// (row b = i * T_l + t, buffers.py:541-548); SRC_TASKS: from the buffer, task-major with per-task counts
+// (row offs[t] + j = store[idx[offs[t] + j]][t], buffers.py:496-519; offs [T_l + 1]); SRC_USER: from a user batch.
+enum GatherSrc { SRC_USER = 0, SRC_INTERLEAVED = 1, SRC_TASKS = 2 };
+template <int SRC>
 __global__ __launch_bounds__(256) void gather_kernel(GatherParams p, const float* __restrict__ u_obs,
                                                      const float* __restrict__ u_act, const float* __restrict__ u_nobs,
                                                      const float* __restrict__ u_done, const float* __restrict__ u_rew,
@@ -134,12 +192,18 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherParams p, const float
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
+  constexpr bool SRC_STORE = SRC != SRC_USER;
   const int D = p.obs_dim, A = p.act_dim;
-  const int t = b % p.T_l;
+  int t = b % p.T_l;
   const float* rec = nullptr;
-  if (SRC_STORE) {
+  if (SRC == SRC_INTERLEAVED) {
     const int i = b / p.T_l;
     rec = p.store + ((long long)p.idx[i] * p.T_l + t) * p.R;
+  }
+  if (SRC == SRC_TASKS) {
+    t = 0;
+    while (t + 1 < p.T_l && p.offs[t + 1] <= b) ++t;  // the task whose range holds b (empty tasks skipped)
+    rec = p.store + ((long long)p.idx[b] * p.T_l + t) * p.R;
   }
   float* xa = p.xa + (long long)b * p.ld_a;
   float* xan = p.xa_next + (long long)b * p.ld_a;
@@ -211,7 +275,8 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherParams p, const float
     p.rew[b] = r;
     p.done[b] = d;
     int local = first - p.task_begin;
-    const bool ok = ones == 1 && n_ones == 1 && bad == 0 && first == n_first && local >= 0 && local < p.T_l;
+    const bool ok = ones == 1 && n_ones == 1 && bad == 0 && first == n_first && local >= 0 && local < p.T_l &&
+                    (SRC != SRC_TASKS || local == t);
     if (!ok) {
       atomicOr(p.err, 1);
       local = 0;
@@ -222,13 +287,19 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherParams p, const float
 
 void replay_gather(const GatherParams& p, hipStream_t st) {
   const int B = p.n * p.T_l;
-  hipLaunchKernelGGL((gather_kernel<true>), dim3((B + 3) / 4), dim3(256), 0, st, p, nullptr, nullptr, nullptr,
+  hipLaunchKernelGGL((gather_kernel<SRC_INTERLEAVED>), dim3((B + 3) / 4), dim3(256), 0, st, p, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, B);
+}
+
+void replay_gather_tasks(const GatherParams& p, hipStream_t st) {
+  const int B = p.n * p.T_l;
+  hipLaunchKernelGGL((gather_kernel<SRC_TASKS>), dim3((B + 3) / 4), dim3(256), 0, st, p, nullptr, nullptr, nullptr,
                      nullptr, nullptr, B);
 }
 
 void batch_scatter(const GatherParams& p, const float* obs, const float* act, const float* nobs, const float* done,
                    const float* rew, int B, hipStream_t st) {
-  hipLaunchKernelGGL((gather_kernel<false>), dim3((B + 3) / 4), dim3(256), 0, st, p, obs, act, nobs, done, rew, B);
+  hipLaunchKernelGGL((gather_kernel<SRC_USER>), dim3((B + 3) / 4), dim3(256), 0, st, p, obs, act, nobs, done, rew, B);
 }
 
 // ------------------------------------------------------------------ synthetic fill (bench)

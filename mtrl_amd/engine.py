@@ -190,14 +190,52 @@ class MTSACEngine:
         self.set_rng_state(np.random.default_rng(seed).bit_generator.state)
 
     def sample(self):
+        """(indices, (obs, act, next_obs, done, rew)) of one device sample: ``batch_per_task`` indices and
+        interleaved rows i*T + t, or, with per-task batch sizes set, one index per row and task-major rows."""
         n = self.config.batch_per_task
         B, D, A = self.B, self.obs_dim, self.action_dim
-        idx = np.empty(n, np.int64)
+        idx = np.empty(B if self.task_batch_sizes_set() else n, np.int64)
         obs, nobs = np.empty((B, D), np.float32), np.empty((B, D), np.float32)
         act, done, rew = np.empty((B, A), np.float32), np.empty((B, 1), np.float32), np.empty((B, 1), np.float32)
         check(self.lib.mtsac_sample(self._h, idx.ctypes.data, obs.ctypes.data, act.ctypes.data, nobs.ctypes.data,
                                     done.ctypes.data, rew.ctypes.data))
         return idx, (obs, act, nobs, done, rew)
+
+    # ------------------------------------------------------------------ per-task batch sizes (include/mtsac.h)
+    def set_task_batch_sizes(self, sizes) -> None:
+        """Per-task batch sizes [T] (>= 0, summing to B) for the step's own device sampling -- ``sample``,
+        ``update()`` without a batch, ``update_many`` -- or None: back to ``batch_per_task`` rows per task."""
+        if sizes is None:
+            check(self.lib.mtsac_set_task_batch_sizes(self._h, None))
+            return
+        a = np.asarray(sizes)
+        if a.shape != (self.T_l,):
+            raise ValueError(f"task batch sizes must have shape ({self.T_l},), got {a.shape}")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("task batch sizes must be integers")
+        a = np.ascontiguousarray(a, np.int32)
+        check(self.lib.mtsac_set_task_batch_sizes(self._h, a.ctypes.data))
+
+    def task_batch_sizes_set(self) -> bool:
+        out = np.empty(self.T_l, np.int32)
+        return check(self.lib.mtsac_get_task_batch_sizes(self._h, out.ctypes.data)) == 1
+
+    def task_batch_sizes(self) -> np.ndarray:
+        """The sizes in force (``batch_per_task`` each when none are set)."""
+        out = np.empty(self.T_l, np.int32)
+        check(self.lib.mtsac_get_task_batch_sizes(self._h, out.ctypes.data))
+        return out
+
+    def set_task_loss_logging(self, on: bool) -> None:
+        """Per-task loss terms of the plain step (one more launch per step while on)."""
+        check(self.lib.mtsac_set_task_loss_logging(self._h, 1 if on else 0))
+
+    def task_losses(self) -> np.ndarray:
+        """[2][T]: the last plain step's per-task mean critic (0) and actor (1) loss terms; 0 for a task
+        without rows."""
+        out = np.empty((2, self.T_l), np.float32)
+        check(self.lib.mtsac_get_task_losses(self._h, out.ctypes.data))
+        return out
 
     # ------------------------------------------------------------------ update
     def update(self, batch=None, eps_next=None, eps_cur=None) -> None:
