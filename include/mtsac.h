@@ -444,11 +444,17 @@ int mtsac_task_gradnorm_solve(mtsac_engine* h, int which, const float* task_loss
  * bound is the one documented at enum mtsac_precision whatever the engine's precision.
  * which: 0 actor, 1 critic.  mtsac_get_network_scores: scores [E][D][W] (normalised), counts [E][D] of the
  * last call with bit 0; mtsac_network_gram_dim: r; mtsac_get_network_gram: one [r][r] matrix of the last call
- * with bit 1.  The scratch is allocated at the first call that needs it and freed with the engine. */
+ * with bit 1.  The scratch is allocated at the first call that needs it and freed with the engine.
+ * mtsac_network_eigvals: the eigenvalues of the Grams of the last call with bit 1, solved on the device
+ * (Householder reduction and bisection): lam [E][D][r] ascending, flags [E][D] (nonzero:
+ * that Gram held a non-finite entry and its row of lam is NaN).  The solve runs in place: the Grams of `which`
+ * are consumed, and mtsac_get_network_gram and a second mtsac_network_eigvals for it return -22 until the next
+ * mtsac_network_metrics call with bit 1.  -22 without such a call, -95 on a task-sharded engine. */
 int mtsac_network_metrics(mtsac_engine* h, const mtsac_batch* batch, const float* eps, int32_t what, float threshold);
 int mtsac_get_network_scores(mtsac_engine* h, int which, float* scores, int32_t* counts);
 int mtsac_network_gram_dim(const mtsac_engine* h, int which);
 int mtsac_get_network_gram(mtsac_engine* h, int which, int32_t member, int32_t layer, double* gram);
+int mtsac_network_eigvals(mtsac_engine* h, int which, double* lam, int32_t* flags);
 
 #ifdef __cplusplus
 }

@@ -370,6 +370,18 @@ int mtsac_debug_act_gram(int Z, int M, int W, int ld, const float* H, double* gr
  * layer, ms[1] the Grams (0 for a part the call did not run). */
 int mtsac_debug_network_metrics_ms(struct mtsac_engine* engine, double* ms /* 2 */);
 
+/* The two symmetric-eigenvalue kernels alone (symeig.hip) on host arrays: Z symmetric
+ * matrices A [Z][r][r] (both triangles, read only from the caller's side; the device copy is reduced in place
+ * between guard bands and followed by r words of NaN).  lam [Z][r] ascending, flags [Z] (bit 0: a non-finite
+ * entry, bit 1: a non-finite tridiagonal form; either gives an all-NaN row); d [Z][r], e [Z][r-1] the
+ * tridiagonal form, each may be NULL.  -22 for Z < 1, Z > 64, r < 1, r > 8192 or a NULL A, lam or flags.
+ * Accepts arbitrary doubles; the kernels are written for Grams of fp32 activations, |a_ij| <= 2^24 * 2^256 with
+ * nonzero entries >= 2^-298, where the squares of a column and their sums stay inside fp64's normal range. */
+int mtsac_debug_sym_eigvals(int Z, int r, const double* A, double* lam, double* d, double* e, int32_t* flags);
+/* HIP-event durations of the last mtsac_network_eigvals call for `which`: ms[0] the reduction to tridiagonal
+ * form, ms[1] the bisection; launches: the kernel launches and memsets of that call (may be NULL). */
+int mtsac_debug_network_eigvals_ms(struct mtsac_engine* engine, int which, double* ms /* 2 */, int32_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,9 +177,12 @@ SIGNATURES = {
     "mtsac_get_network_scores": (ctypes.c_int, [P, ctypes.c_int, P, P]),
     "mtsac_network_gram_dim": (ctypes.c_int, [P, ctypes.c_int]),
     "mtsac_get_network_gram": (ctypes.c_int, [P, ctypes.c_int, I32, I32, P]),
+    "mtsac_network_eigvals": (ctypes.c_int, [P, ctypes.c_int, P, P]),
     "mtsac_debug_act_stats": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_float, P, P, P]),
     "mtsac_debug_act_gram": (ctypes.c_int, [ctypes.c_int] * 4 + [P, P, P]),
     "mtsac_debug_network_metrics_ms": (ctypes.c_int, [P, P]),
+    "mtsac_debug_sym_eigvals": (ctypes.c_int, [ctypes.c_int] * 2 + [P] * 5),
+    "mtsac_debug_network_eigvals_ms": (ctypes.c_int, [P, ctypes.c_int, P, P]),
     "mtsac_debug_gemm_bench": (ctypes.c_int, [ctypes.c_int] * 8 + [PD]),
     "mtsac_debug_gemm_x3p": (ctypes.c_int, [ctypes.c_int] * 4 + [P, ctypes.c_int, P, ctypes.c_int, P, P, P, P]),
     "mtsac_debug_gemm_x3p_kmajor": (ctypes.c_int, [ctypes.c_int] * 5 + [P, P, P]),

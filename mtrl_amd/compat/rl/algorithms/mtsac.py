@@ -435,7 +435,9 @@ class MTSAC(OffPolicyAlgorithm):
         if n != self._cfg_kwargs["batch_per_task"]:  # raises once a buffer lives in the engine
             self._rebuild(batch_per_task=n, capacity=max(self._cfg_kwargs["capacity"], n))
         eps = self._rng.standard_normal((obs.shape[0], self.engine.action_dim)).astype(np.float32)
-        return self, compute_metrics(self.engine, metrics, obs, eps)
+        # where srank's eigenvalues are solved: "host" (numpy) or "device" 
+        eig = os.environ.get("MTSAC_NETWORK_METRICS_EIG", "host")
+        return self, compute_metrics(self.engine, metrics, obs, eps, eig=eig)
 
     # ------------------------------------------------------------------ state (checkpoint)
     def state_dict(self) -> dict[str, np.ndarray]:

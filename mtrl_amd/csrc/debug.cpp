@@ -441,6 +441,41 @@ int mtsac_debug_act_gram(int Z, int M, int W, int ld, const float* H, double* gr
   return g.back(gram, a.gram, (size_t)Z * r * r) ? 0 : -5;
 }
 
+// ---- the symmetric eigenvalue kernels (symeig.hip) ----
+// Accepts arbitrary doubles.  The kernels are written for Grams of fp32 activations: |a_ij| <= 2^24 * 2^256 and
+// nonzero entries >= 2^-298, so the squares of a column and their sums stay inside fp64's normal range and the
+// reflector's norm is formed without scaling.  Outside that domain a norm may overflow or lose its small
+// terms; an overflow ends as a non-finite tridiagonal form, that is an all-NaN row and flag bit 1.
+int mtsac_debug_sym_eigvals(int Z, int r, const double* A, double* lam, double* d, double* e, int32_t* flags) {
+  if (Z < 1 || Z > 64 || r < 1 || r > SYM_EIG_MAX_ORDER || !A || !lam || !flags) return -22;
+  if (!outputs_distinct({lam, d, e, flags})) return -22;
+  if (hipSetDevice(0) != hipSuccess) return -5;
+  const size_t n = (size_t)Z * r * r, Zr = (size_t)Z * r, Ze = (size_t)Z * (r - 1);
+  Guarded g;
+  SymEig s{};
+  // in place: a store outside the matrices shows in the bands, a read past the last one in r words of NaN
+  s.A = g.out<double>(n + r, "A");
+  if (s.A && hipMemcpy(s.A, A, n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) g.ok = false;
+  s.Z = Z;
+  s.r = r;
+  s.d = g.out<double>(Zr, "d");
+  s.e = g.out<double>(Ze, "e");
+  s.v = g.out<double>(2 * Zr, "v");
+  s.p = g.out<double>(2 * Zr, "p");
+  s.part = g.out<double>((size_t)Z * sym_tridiag_parts(r), "part");
+  s.tau = g.out<double>((size_t)2 * Z, "tau");
+  s.lam = g.out<double>(Zr, "lam");
+  s.flags = g.out<int>((size_t)Z, "flags");
+  if (!g.ok) return -12;
+  sym_tridiag(s, nullptr);
+  tridiag_eigvals(s, nullptr);
+  int rc = 0;
+  if ((rc = sync_rc("sym_eigvals")) || (rc = g.check())) return rc;
+  if (d && !g.back(d, s.d, Zr)) return -5;
+  if (e && Ze && !g.back(e, s.e, Ze)) return -5;
+  return g.back(lam, s.lam, Zr) && g.back(flags, s.flags, (size_t)Z) ? 0 : -5;
+}
+
 int mtsac_debug_head_backward(int form, int flags, int B, int T_l, int E, int W, int hd, const int* task, const float* h,
                               const float* Wh, const float* dout, const float* dq, float* dz, float* dbp, float* db,
                               float* planes, float* dWh, float* dbh, int* counts, int* rows, int* info) {

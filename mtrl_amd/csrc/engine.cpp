@@ -531,6 +531,8 @@ struct mtsac_engine {
     for (hipEvent_t e : evpool) (void)hipEventDestroy(e);
     for (hipEvent_t x : nm.ev)
       if (x) (void)hipEventDestroy(x);
+    for (hipEvent_t x : nm.eig_ev)
+      if (x) (void)hipEventDestroy(x);
     for (hipStream_t x : {st, s1, s2, s3, s4, sa})
       if (x) (void)hipStreamDestroy(x);
     if (counted_lanes) {
@@ -2091,6 +2093,12 @@ struct mtsac_engine {
     int last = 0;  // `what` of the last call that completed
     hipEvent_t ev[3] = {};
     double ms[2] = {0.0, 0.0};
+    // the device eigen solve of the Grams (symeig.hip): scratch per network, allocated at its first solve
+    SymEig eig[2] = {};
+    bool consumed[2] = {false, false};  // the solve ran in place on gram[w]
+    hipEvent_t eig_ev[3] = {};
+    double eig_ms[2][2] = {};
+    int eig_launches[2] = {0, 0};
   } nm;
   Net& nm_net(int which) { return which == 0 ? actor : critic; }
   int nm_dim(int which) const { return act_gram_dim(B, which == 0 ? actor.width : critic.width); }
@@ -2117,6 +2125,25 @@ struct mtsac_engine {
       if (!e && hipEventCreate(&e) != hipSuccess) return fail(-5, "hipEventCreate");
     // alloc()'s null-stream zero fills before the engine streams use the buffers
     if (fresh && hipDeviceSynchronize() != hipSuccess) return fail(-5, "device synchronize");
+    return 0;
+  }
+
+  int ensure_eig_buffers(int w) {
+    int rc = 0;
+    SymEig& s = nm.eig[w];
+    if (!s.d) {
+      const Net& net = nm_net(w);
+      const size_t Z = (size_t)net.E * net.depth, r = (size_t)nm_dim(w);
+      if ((rc = alloc(&s.d, Z * r)) || (rc = alloc(&s.e, Z * r)) || (rc = alloc(&s.v, 2 * Z * r)) ||
+          (rc = alloc(&s.p, 2 * Z * r)) || (rc = alloc(&s.part, Z * sym_tridiag_parts((int)r))) ||
+          (rc = alloc(&s.tau, 2 * Z)) || (rc = alloc(&s.lam, Z * r)) || (rc = alloc(&s.flags, Z)))
+        return rc;
+      s.Z = (int)Z;
+      s.r = (int)r;
+      if (hipDeviceSynchronize() != hipSuccess) return fail(-5, "device synchronize");
+    }
+    for (hipEvent_t& e : nm.eig_ev)
+      if (!e && hipEventCreate(&e) != hipSuccess) return fail(-5, "hipEventCreate");
     return 0;
   }
 
@@ -3909,6 +3936,7 @@ int mtsac_network_metrics(mtsac_engine* h, const mtsac_batch* b, const float* ep
     h->nm.ms[k] = hipEventElapsedTime(&ms, h->nm.ev[k], h->nm.ev[k + 1]) == hipSuccess ? (double)ms : 0.0;
   }
   h->nm.last = what;
+  if (what & 2) h->nm.consumed[0] = h->nm.consumed[1] = false;
   return 0;
 }
 
@@ -3931,10 +3959,50 @@ int mtsac_get_network_gram(mtsac_engine* h, int which, int32_t member, int32_t l
   if (!h || !gram || (which != 0 && which != 1)) return fail(-22, "which: 0 actor, 1 critic; gram required");
   if (!(h->nm.last & 2)) return fail(-22, "no Gram matrices yet (mtsac_network_metrics with what bit 1)");
   const Net& net = h->nm_net(which);
+  if (h->nm.consumed[which])
+    return fail(-22, "the Gram matrices were consumed by mtsac_network_eigvals (the solve runs in place)");
   if (member < 0 || member >= net.E || layer < 0 || layer >= net.depth) return fail(-22, "member or layer out of range");
   const size_t rr = (size_t)h->nm_dim(which) * h->nm_dim(which);
   HIP_TRY(hipMemcpy(gram, h->nm.gram[which] + ((size_t)member * net.depth + layer) * rr, sizeof(double) * rr,
                     hipMemcpyDefault));
+  return 0;
+}
+
+int mtsac_network_eigvals(mtsac_engine* h, int which, double* lam, int32_t* flags) {
+  if (!h || !lam || !flags || (which != 0 && which != 1)) return fail(-22, "which: 0 actor, 1 critic; lam and flags required");
+  if (int rc = h->geo_guard()) return rc;
+  if (h->T_l != h->T_g) return fail(-95, "network metrics need every task on one engine (unsharded)");
+  if (!(h->nm.last & 2)) return fail(-22, "no Gram matrices yet (mtsac_network_metrics with what bit 1)");
+  if (h->nm.consumed[which]) return fail(-22, "the Gram matrices were consumed by an earlier mtsac_network_eigvals");
+  if (h->nm_dim(which) > SYM_EIG_MAX_ORDER) return fail(-22, "Gram order above 8192: no device eigen solve");
+  if (int rc = h->ensure_eig_buffers(which)) return rc;
+  SymEig& s = h->nm.eig[which];
+  s.A = h->nm.gram[which];  // [E][D][r][r], dense
+  h->nm.consumed[which] = true;
+  HIP_TRY(hipEventRecord(h->nm.eig_ev[0], h->st));
+  sym_tridiag(s, h->st);
+  HIP_TRY(hipEventRecord(h->nm.eig_ev[1], h->st));
+  tridiag_eigvals(s, h->st);
+  HIP_TRY(hipEventRecord(h->nm.eig_ev[2], h->st));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(h->st));
+  for (int k = 0; k < 2; ++k) {
+    float ms = 0.f;
+    h->nm.eig_ms[which][k] =
+        hipEventElapsedTime(&ms, h->nm.eig_ev[k], h->nm.eig_ev[k + 1]) == hipSuccess ? (double)ms : 0.0;
+  }
+  h->nm.eig_launches[which] = sym_tridiag_launches(s.r) + 1;
+  const size_t Z = (size_t)s.Z;
+  HIP_TRY(hipMemcpy(lam, s.lam, sizeof(double) * Z * s.r, hipMemcpyDefault));
+  HIP_TRY(hipMemcpy(flags, s.flags, sizeof(int32_t) * Z, hipMemcpyDefault));
+  return 0;
+}
+
+int mtsac_debug_network_eigvals_ms(mtsac_engine* h, int which, double* ms, int32_t* launches) {
+  if (!h || !ms || (which != 0 && which != 1)) return fail(-22, "which: 0 actor, 1 critic; ms required");
+  ms[0] = h->nm.eig_ms[which][0];
+  ms[1] = h->nm.eig_ms[which][1];
+  if (launches) *launches = h->nm.eig_launches[which];
   return 0;
 }
 

@@ -783,6 +783,29 @@ struct ActGram {
 int act_gram_dim(int M, int W);
 void act_gram(const ActGram& g, hipStream_t st);
 
+// ------------------------------------------------------------------ symmetric eigenvalues (symeig.hip; DESIGN.md
+// section 19).  Z dense symmetric fp64 matrices A [Z][r][r] (both triangles, bitwise symmetric,
+// 1 <= r <= SYM_EIG_MAX_ORDER).
+// sym_tridiag reduces them in place (A is destroyed) to d [Z][r], e [Z][r-1] by unblocked Householder steps and
+// sets flags[z] bit 0 where a matrix holds a non-finite entry; tridiag_eigvals bisects for lam [Z][r], ascending
+// (a zero matrix: exact zeros; a flagged matrix or a non-finite d / e, flag bit 1: all NaN).  Scratch: v, p
+// [2][Z][r], part [Z][sym_tridiag_parts(r)], tau [2][Z].  Every sum has one fixed order and every grid is per
+// matrix: bitwise equal run to run and whatever else the batch holds.  No float atomics; phases are ordered
+// by the stream alone.
+struct SymEig {
+  double* A;
+  int Z, r;
+  double *d, *e;
+  double *v, *p, *part, *tau;
+  double* lam;
+  int* flags;
+};
+constexpr int SYM_EIG_MAX_ORDER = 8192;  // tridiag_eigvals keeps 16 r bytes in LDS
+int sym_tridiag_parts(int r);
+int sym_tridiag_launches(int r);  // kernel launches and memsets of one sym_tridiag call
+void sym_tridiag(const SymEig& s, hipStream_t st);
+void tridiag_eigvals(const SymEig& s, hipStream_t st);
+
 // sets what mtsac_last_error returns on this thread (engine.cpp; the debug entry points name a
 // written guard band through it)
 void set_last_error(const char* msg);

@@ -296,13 +296,17 @@ class MTSACEngine:
 
     # ------------------------------------------------------------------ network health metrics
     def network_metrics(self, observations=None, eps=None, dormant: bool = True, gram: bool = True,
-                        threshold: float = 0.1) -> dict:
+                        threshold: float = 0.1, eig: str = "host") -> dict:
         """Dormant-neuron statistics and activation Grams of every trunk layer (include/mtsac.h,
         mtsac_network_metrics), nothing updated.  ``observations`` [B][obs_dim] (rows interleaved i*T + t) or
         None (a device sample); ``eps`` [B][A] or None (device noise).  Returns ``{"actor": r, "critic": r}`` with
         ``r = {"members": E, "depth": D, "width": W, "scores": [E][D][W] float32 normalised scores,
         "counts": [E][D] int32, "gram": E lists of D float64 [r][r] matrices}`` (the parts not asked for: None).
+        ``eig="device"`` with ``gram``: the Grams stay on the device and are solved there (``network_eigvals``);
+        ``r["gram"]`` is None and ``r["eigvals"]`` [E][D][r] float64 ascending, ``r["eig_flags"]`` [E][D] int32.
         mtrl_amd/netmetrics.py makes the LogDict of them."""
+        if eig not in ("host", "device"):
+            raise ValueError(f"eig must be 'host' or 'device', not {eig!r}")
         c = self.config
         what = (1 if dormant else 0) | (2 if gram else 0)
         bp, keep = None, None
@@ -320,7 +324,9 @@ class MTSACEngine:
                 r["scores"], r["counts"] = np.empty((E, D, W), np.float32), np.empty((E, D), np.int32)
                 check(self.lib.mtsac_get_network_scores(self._h, which, r["scores"].ctypes.data,
                                                         r["counts"].ctypes.data))
-            if gram:
+            if gram and eig == "device":
+                r["eigvals"], r["eig_flags"] = self.network_eigvals(which)
+            elif gram:
                 n = check(self.lib.mtsac_network_gram_dim(self._h, which))
                 r["gram"] = [[np.empty((n, n), np.float64) for _ in range(D)] for _ in range(E)]
                 for e in range(E):
@@ -328,6 +334,24 @@ class MTSACEngine:
                         check(self.lib.mtsac_get_network_gram(self._h, which, e, i, r["gram"][e][i].ctypes.data))
             out[name] = r
         return out
+
+    def network_eigvals(self, which: int):
+        """Eigenvalues of the Grams of the last ``network_metrics`` call with ``gram``, solved on the device
+        (mtsac_network_eigvals).  ``which``: 0 actor, 1 critic.  Returns
+        ``(lam [E][D][r] float64 ascending, flags [E][D] int32)``; a nonzero flag marks a Gram with a non-finite
+        entry, whose eigenvalues are NaN.  The solve consumes the Grams of ``which``."""
+        c = self.config
+        E, D = ((1, c.actor_depth), (c.num_critics, c.critic_depth))[which]
+        n = check(self.lib.mtsac_network_gram_dim(self._h, which))
+        lam, flags = np.empty((E, D, n), np.float64), np.empty((E, D), np.int32)
+        check(self.lib.mtsac_network_eigvals(self._h, which, lam.ctypes.data, flags.ctypes.data))
+        return lam, flags
+
+    def network_eigvals_kernel_ms(self, which: int) -> tuple[float, float, int]:
+        """HIP-event time (ms) of the last ``network_eigvals(which)``: reduction, bisection; and its launches."""
+        ms, n = (ctypes.c_double * 2)(), ctypes.c_int32(0)
+        check(self.lib.mtsac_debug_network_eigvals_ms(self._h, which, ms, ctypes.byref(n)))
+        return float(ms[0]), float(ms[1]), int(n.value)
 
     def network_metrics_kernel_ms(self) -> tuple[float, float]:
         """HIP-event time of the last network_metrics call's statistics and Gram kernels (ms)."""

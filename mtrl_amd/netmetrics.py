@@ -44,6 +44,11 @@ def singular_values_from_gram(gram) -> np.ndarray:
     return np.sqrt(np.maximum(lam, 0.0))[::-1]
 
 
+def singular_values_from_eigvals(lam) -> np.ndarray:
+    """sigma (descending) from the Gram's eigenvalues in ascending order (the device solve)."""
+    return np.sqrt(np.maximum(np.asarray(lam, np.float64), 0.0))[::-1]
+
+
 def srank_from_gram(gram, delta: float = SRANK_DELTA) -> int:
     return srank_from_singular_values(singular_values_from_gram(gram), delta)
 
@@ -94,15 +99,34 @@ def expected_keys(depth_actor: int, depth_critic: int, num_critics: int) -> list
     return keys
 
 
-def compute_metrics(engine, metrics, observations=None, eps=None, threshold: float = DORMANT_THRESHOLD) -> dict:
-    """One device pass on ``engine`` and the LogDict.  Nothing runs when ``metrics`` enables neither group."""
+def _sranks(r, e) -> list[int]:
+    """srank of every layer of member e from one network's ``network_metrics`` result (either eig path)."""
+    if r["gram"] is None:
+        return [srank_from_singular_values(singular_values_from_eigvals(lam)) for lam in r["eigvals"][e]]
+    return [srank_from_gram(g) for g in r["gram"][e]]
+
+
+def compute_metrics(engine, metrics, observations=None, eps=None, threshold: float = DORMANT_THRESHOLD,
+                    eig: str = "host") -> dict:
+    """One device pass on ``engine`` and the LogDict.  Nothing runs when ``metrics`` enables neither group.
+    ``eig``: where the Grams' eigenvalues are computed, "host" (``numpy.linalg.eigvalsh`` on copies of the Grams)
+    or "device" (the engine's Householder + bisection solve; raises on a non-finite Gram)."""
     from .compat.config.utils import Metrics
 
     dormant = bool(metrics.is_enabled(Metrics.DORMANT_NEURONS))
     srank = bool(metrics.is_enabled(Metrics.SRANK))
     if not (dormant or srank):
         return {}
-    out = engine.network_metrics(observations, eps, dormant=dormant, gram=srank, threshold=threshold)
+    if eig not in ("host", "device"):
+        raise ValueError(f"eig must be 'host' or 'device', not {eig!r}")
+    if eig == "device" and srank:
+        out = engine.network_metrics(observations, eps, dormant=dormant, gram=True, threshold=threshold, eig="device")
+        for net in ("actor", "critic"):
+            if np.any(out[net]["eig_flags"]):
+                raise FloatingPointError(f"non-finite activation Gram in the {net} trunk (flags "
+                                         f"{out[net]['eig_flags'].tolist()}): no srank")
+    else:  # the call the host path has always made
+        out = engine.network_metrics(observations, eps, dormant=dormant, gram=srank, threshold=threshold)
     members = {}
     for which, net in enumerate(("actor", "critic")):
         r = out[net]
@@ -110,5 +134,5 @@ def compute_metrics(engine, metrics, observations=None, eps=None, threshold: flo
             name = "actor" if which == 0 else f"critic_{e}"
             members[name] = {"width": r["width"],
                              "counts": r["counts"][e] if dormant else None,
-                             "srank": [srank_from_gram(g) for g in r["gram"][e]] if srank else None}
+                             "srank": _sranks(r, e) if srank else None}
     return network_logs(metrics, members)
