@@ -79,20 +79,19 @@ int mtsac_debug_gemm_x3f_ragged(int flags, int B, int N, int K, const float* A, 
 int mtsac_debug_gemm_fwd_bench(int which, int epi, int batch, int M, int N, int K, int iters, double* ms_per_launch);
 /* Rows per gemm_x3s tile / 16 (TI, 4..8) the cost model picks for an M x N output, batch entries. */
 int mtsac_debug_x3s_ti(int M, int N, int batch);
-// DrQ conv channel groups per lane (fwd: output channels, bwd: input channels; 0 = the engine's
-// choice); returns the previous fwd | bwd << 8.  Experiments only.
+// The DrQ conv switches (tests, experiments, A/B runs).  They are read when an engine is created and
+// when a debug conv entry point below is called -- the one place that plans a conv -- so an engine
+// that exists keeps the kernels and buffer sizes it was created with whatever is set afterwards.
+// Each setter returns the previous value.
+// Channel groups per lane of the one-lane-per-pixel kernels (fwd: output channels, bwd: input
+// channels; 0 = the plan's choice); returns fwd | bwd << 8.
 int mtsac_debug_drq_groups(int fwd, int bwd);
-// DrQ convolutions on f32 MFMA (experiment, measured slower than the VALU kernels): bit 1 forward,
-// 2 data grad, 4 weight grad (default 0 = the VALU kernels).  Returns the previous mask; < 0 queries.
-int mtsac_debug_drq_mfma(int mask);
 // The pre-round-6 DrQ conv kernels (one lane per pixel, im2col weight grad) instead of the row-tile
 // ones: bit 1 forward, 2 data grad, 4 weight grad; bit 8 runs the row-tile kernels at every shape
 // (past the measured per-shape choice); bit 16 turns the split2h MFMA convs off, bit 32 runs them at
-// every shape they support.  Returns the previous mask; < 0 queries.
+// every shape they support.  Default: MTSAC_DRQ_LEGACY in the environment, or 0.  < 0 queries.
 int mtsac_debug_drq_legacy(int mask);
-// The row-tile conv weight grad's grid cap (> 0 sets, 0 restores the per-shape default, < 0 queries;
-// returns the previous).  Engines size their partial buffers at creation: change it only before
-// creating one.  Experiments.
+// The row-tile conv weight grad's grid cap (> 0 sets, 0 restores the per-shape default, < 0 queries).
 int mtsac_debug_drq_wgrad_blocks(int cap);
 // Mean microseconds per launch of one DrQ conv pass on random operands: kind 0 forward (ReLU in,
 // residual), 1 data gradient (mask, residual), 2 weight-gradient partials.  -22 bad arguments.
@@ -114,10 +113,9 @@ int mtsac_debug_drq_conv_bench(int kind, int B, int H, int W, int ci, int co, in
 int mtsac_debug_drq_conv(int kind, int flags, int B, int B1, int H, int W, int ci, int co, const float* x,
                          const float* w, const float* bias, const float* w2, const float* bias2, const float* aux,
                          const float* aux2, float* out, float* out2);
-/* What the conv launcher of `kind` runs at this shape under the current masks: out[0] family
- * (0 one lane per pixel / im2col, 1 row tiles, 2 split2h MFMA, 3 f32 MFMA), out[1] rows per tile,
- * out[2] tiles per image (0 when not tiled), out[3] grid blocks.  The launchers decide through the
- * same functions. */
+/* The plan of a conv of `kind` at this shape under the current switches: out[0] family (0 one lane
+ * per pixel / im2col, 1 row tiles, 2 split2h MFMA), out[1] rows per tile, out[2] tiles per image
+ * (0 when not tiled), out[3] grid blocks.  The launchers run from such a plan. */
 int mtsac_debug_drq_conv_path(int kind, int B, int H, int W, int ci, int co, int* out);
 /* Max pool 3x3 / stride 2 / SAME forward then backward: out, arg [B][Ho][Wo][C] (argmax tap 0..8),
  * din [B][H][W][C] from dout [B][Ho][Wo][C]; C a multiple of 4. */

@@ -193,7 +193,6 @@ SIGNATURES = {
     "mtsac_debug_gemm_fwd_bench": (ctypes.c_int, [ctypes.c_int] * 7 + [PD]),
     "mtsac_debug_x3s_ti": (ctypes.c_int, [ctypes.c_int] * 3),
     "mtsac_debug_drq_groups": (ctypes.c_int, [ctypes.c_int] * 2),
-    "mtsac_debug_drq_mfma": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_drq_legacy": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_drq_wgrad_blocks": (ctypes.c_int, [ctypes.c_int]),
     "mtsac_debug_drq_conv_bench": (ctypes.c_int, [ctypes.c_int] * 7 + [ctypes.POINTER(ctypes.c_double)]),

@@ -44,36 +44,24 @@ PlaneRec* rec_out(Guarded& g, int e, const char* name) {
 
 extern "C" {
 
-// DrQ conv channel groups per lane (0 = the engine's choice); returns the previous fwd | bwd << 8
+// The DrQ conv switches (drq::ConvSwitches, meanings in mtsac_debug.h).  drq::conv_plan reads them
+// when an engine is created and when a debug conv entry point is called; an engine that exists
+// keeps its plans.  Each setter returns the previous value.
 int mtsac_debug_drq_groups(int fwd, int bwd) {
-  const int old = drq::g_drq_fwd_g | (drq::g_drq_bwd_g << 8);
-  drq::g_drq_fwd_g = fwd;
-  drq::g_drq_bwd_g = bwd;
+  drq::ConvSwitches& sw = drq::conv_switches();
+  const int old = sw.fwd_g | (sw.bwd_g << 8);
+  sw.fwd_g = fwd;
+  sw.bwd_g = bwd;
   return old;
 }
-
-// DrQ convs on f32 MFMA (bit 1 forward, 2 data grad, 4 weight grad) or the VALU kernels; returns the
-// previous mask (< 0: query only)
-int mtsac_debug_drq_mfma(int mask) {
-  const int old = drq::g_drq_mfma;
-  if (mask >= 0) drq::g_drq_mfma = mask & 7;
+int mtsac_debug_drq_legacy(int mask) {  // < 0: query only
+  const int old = drq::conv_switches().legacy;
+  if (mask >= 0) drq::conv_switches().legacy = mask & 63;
   return old;
 }
-
-// the pre-round-6 DrQ conv kernels (bit 1 forward, 2 data grad, 4 weight grad) or the row-tile ones;
-// returns the previous mask (< 0: query only)
-int mtsac_debug_drq_legacy(int mask) {
-  const int old = drq::g_drq_legacy;
-  if (mask >= 0) drq::g_drq_legacy = mask & 63;
-  return old;
-}
-
-// the row-tile conv weight grad's grid cap (> 0 sets, 0 restores the per-shape default; < 0 queries;
-// returns the previous); engines created before a change keep partial buffers sized for the old cap,
-// so set it before creating one (experiments)
-int mtsac_debug_drq_wgrad_blocks(int cap) {
-  const int old = drq::g_drq_wg_blocks;
-  if (cap >= 0) drq::g_drq_wg_blocks = cap;
+int mtsac_debug_drq_wgrad_blocks(int cap) {  // 0: the per-shape default; < 0: query only
+  const int old = drq::conv_switches().wg_blocks;
+  if (cap >= 0) drq::conv_switches().wg_blocks = cap;
   return old;
 }
 
@@ -87,16 +75,17 @@ int mtsac_debug_drq_conv_bench(int kind, int B, int H, int W, int ci, int co, in
   return hipDeviceSynchronize() == hipSuccess ? 0 : -5;
 }
 
-// what the conv launcher of `kind` runs at this shape under the current masks (drq::conv_path)
+// the plan of a conv of `kind` at this shape under the current switches (drq::conv_plan)
 int mtsac_debug_drq_conv_path(int kind, int B, int H, int W, int ci, int co, int* out) {
   if (kind < 0 || kind > 2 || B < 1 || H < 1 || W < 1 || !out || !drq::conv_supported(ci, co) ||
       (long long)B * H * W * 16 >= (1LL << 31))
     return -22;
-  const drq::ConvPath p = drq::conv_path(kind, B, H, W, ci, co);
+  const drq::ConvPlan p = drq::conv_plan(kind, B, H, W, ci, co);
+  const bool tiled = p.family != 0;
   out[0] = p.family;
-  out[1] = p.R;
-  out[2] = p.n;
-  out[3] = p.blocks;
+  out[1] = !tiled ? 0 : kind == 2 ? p.wg.R : p.geo.R;
+  out[2] = !tiled ? 0 : kind == 2 ? p.wg.tiles / B : p.geo.n;
+  out[3] = drq::conv_blocks(p, B);
   return 0;
 }
 
@@ -113,6 +102,7 @@ int mtsac_debug_drq_conv(int kind, int flags, int B, int B1, int H, int W, int c
   if (kind == 2 && (!aux || !out2)) return -22;
   if (hipSetDevice(0) != hipSuccess) return -5;
   const size_t np = (size_t)B * H * W, nw = (size_t)9 * ci * co;
+  const drq::ConvPlan pl = drq::conv_plan(kind, B, H, W, ci, co);  // sizes and launches below: this one value
   Guarded g;
   int rc = 0;
   if (kind == 0) {
@@ -121,18 +111,18 @@ int mtsac_debug_drq_conv(int kind, int flags, int B, int B1, int H, int W, int c
     const float* dres = g.in(aux, np * co);
     float* dout = g.out<float>(np * co, "out");
     if (!g.ok) return -12;
-    drq::conv_fwd(dx, dw, dbi, dres, dout, B, H, W, ci, co, (flags & 1) != 0, nullptr, dw2, db2, w2 ? B1 : -1);
+    drq::conv_fwd(pl, dx, dw, dbi, dres, dout, B, (flags & 1) != 0, nullptr, dw2, db2, w2 ? B1 : -1);
     if ((rc = sync_rc("conv_fwd")) || (rc = g.check())) return rc;
     if (!g.back(out, dout, np * co)) return -5;
   } else if (kind == 1) {
     const float *ddout = g.in(x, np * co), *dw = g.in(w, nw), *dmask = g.in(aux, np * ci), *ddres = g.in(aux2, np * ci);
     float* ddin = g.out<float>(np * ci, "din");
     if (!g.ok) return -12;
-    drq::conv_bwd_data(ddout, dw, dmask, ddres, ddin, B, H, W, ci, co, nullptr);
+    drq::conv_bwd_data(pl, ddout, dw, dmask, ddres, ddin, B, nullptr);
     if ((rc = sync_rc("conv_bwd_data")) || (rc = g.check())) return rc;
     if (!g.back(out, ddin, np * ci)) return -5;
   } else {
-    const int G = drq::conv_wgrad_blocks(B, H, W, ci, co), n = (int)nw + co;
+    const int G = pl.rows, n = (int)nw + co;
     const bool defer = (flags & 2) != 0;
     const float *dx = g.in(x, np * ci), *ddout = g.in(aux, np * co);
     float* part = g.out<float>((size_t)G * n, "part");
@@ -142,7 +132,7 @@ int mtsac_debug_drq_conv(int kind, int flags, int B, int B1, int H, int W, int c
     const drq::SumSeg seg{part, ddw, ddb, G, n, (int)nw, 0};
     const drq::SumSeg* dseg = g.in(&seg, 1);
     if (!g.ok) return -12;
-    drq::conv_wgrad(dx, ddout, part, ddw, ddb, B, H, W, ci, co, (flags & 1) != 0, nullptr, defer);
+    drq::conv_wgrad(pl, dx, ddout, part, ddw, ddb, (flags & 1) != 0, nullptr, defer);
     if (defer) drq::sum_parts_multi(dseg, 1, drq::sum_parts_blocks(ci, co), nullptr);
     if ((rc = sync_rc("conv_wgrad")) || (rc = g.check())) return rc;
     if (!g.back(out, ddw, nw) || !g.back(out2, ddb, (size_t)co)) return -5;

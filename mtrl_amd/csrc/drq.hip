@@ -12,6 +12,7 @@
 // partials summed in a fixed order (bitwise reproducible).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "drq_kernels.h"
@@ -451,6 +452,9 @@ struct WgRows {
   static constexpr int PG = 256 / NB;         // pixel groups
   static constexpr int NPF = 8;               // staged float4 per thread per tile
   static constexpr int E4 = CB * CO / 4;      // float4 of one lane's block
+  // RED4 holds one slot per pair of pixel groups (the first step of the kernel's partial-sum tree);
+  // the tree is sized and tested for an even PG only (every CONV_CASES pair gives 28 or 14)
+  static_assert(PG % 2 == 0, "WgRows: the partial-sum scratch assumes an even number of pixel groups");
   static constexpr int RED4 = (PG / 2) * NB * E4;
   static constexpr int LDS4 = RED4 > NPF * 256 ? RED4 : NPF * 256;
 };
@@ -846,220 +850,6 @@ __global__ __launch_bounds__(256) void conv_h2_kernel(const float* __restrict__ 
       }
     }
   }
-}
-
-// ------------------------------------------------------------------ convolutions on f32 MFMA
-// v_mfma_f32_16x16x4_f32 (exact fp32: bit for bit a k-ordered fmaf chain, MI355X_MICROARCH.md) at the
-// FP32 rate, which the VALU kernels above reach only with packed FMAs fed from SGPRs; here the VALU
-// only computes addresses and the operands come straight from L1/L2 one fp32 per lane.
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// Weight gradient as 9 / TPM small GEMMs over pixels: dW[tap][ci][co] = sum_p act(in)[p + off(tap)][ci]
-// * dout[p][co].  M-tile m stacks TPM = 16 / CI taps (rows r: tap m TPM + r / CI, channel r % CI), N = CO
-// (columns >= CO zero), K = pixels, 4 per MFMA (lane slot l >> 4).  A lane's A operand is one input
-// channel of one shifted pixel (16 lanes read 16 consecutive floats), its B operand dout[p][l & 15],
-// shared by every M-tile.  Every load is unconditional (a clamped in-range address, the value selected
-// afterwards): a load under a branch was waited for at the branch's end, one latency per operand.
-// Wave w of a block takes pixels c0 + 16 j + 4 w + slot of the block's chunk; each fp32 MFMA chain runs
-// FLUSH k-steps and is then added into double accumulators (the bias sum is double throughout); the four
-// waves' sums are added in wave order in LDS.  part[g][9 CI CO + CO] as conv_wgrad_kernel.
-template <int CI, int CO, bool RELU_IN>
-__global__ __launch_bounds__(256) void conv_wgrad_mfma_kernel(const float* __restrict__ in, const float* __restrict__ dout,
-                                                              float* __restrict__ part, int B, int H, int W, int chunk) {
-  constexpr int TPM = 16 / CI, MT = (9 + TPM - 1) / TPM;
-  constexpr int NW = 9 * CI * CO;
-  constexpr int FLUSH = 32;
-  static_assert(CI == 4 || CI == 8 || CI == 16, "CI");
-  static_assert(CO == 8 || CO == 16, "CO");
-  __shared__ double red[MT * 256];
-  __shared__ double bred[4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int row = lane & 15, slot = lane >> 4;
-  const int ci = row % CI, tsub = row / CI;
-  const int npix = B * H * W;
-  const int c0 = blockIdx.x * chunk, c1 = min(npix, c0 + chunk);
-  int dys[MT], dxs[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int tap = m * TPM + tsub;
-    dys[m] = tap < 9 ? tap / 3 - 1 : 99;
-    dxs[m] = tap < 9 ? tap % 3 - 1 : 0;
-  }
-  double accd[MT][4];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) accd[m][r] = 0.0;
-  double bsum = 0.0;
-  const bool gcol = row < CO;
-  int p = c0 + 4 * wv + slot;
-  int x = p % W, y = (p / W) % H;
-  const int nsteps = c1 > c0 ? (c1 - c0 + 15) / 16 : 0;
-  // operands of one k-step (this lane's pixel p at (x, y)), loaded one k-step ahead of its MFMAs
-  float av[MT], g = 0.f;
-  auto load = [&](int pp, int xx0, int yy0, float* a, float& gg) {
-    const bool vp = pp < c1;
-    const int pc = vp ? pp : c0;  // an in-range pixel for the unconditional loads
-    const float gl = dout[(long long)pc * CO + (gcol ? row : 0)];
-    gg = (vp && gcol) ? gl : 0.f;
-#pragma unroll
-    for (int m = 0; m < MT; ++m) {
-      const int yy = yy0 + dys[m], xx = xx0 + dxs[m];
-      const bool ok = vp && yy >= 0 && yy < H && xx >= 0 && xx < W;
-      const int q = ok ? pp + dys[m] * W + dxs[m] : pc;
-      const float v = in[(long long)q * CI + ci];
-      a[m] = ok ? (RELU_IN ? fmaxf(v, 0.f) : v) : 0.f;
-    }
-  };
-  auto advance = [&]() {  // this lane's next pixel: 16 on (W >= 4: at most 4 wraps)
-    p += 16;
-    x += 16;
-    while (x >= W) {
-      x -= W;
-      if (++y == H) y = 0;
-    }
-  };
-  if (nsteps > 0) load(p, x, y, av, g);
-  for (int s0 = 0; s0 < nsteps; s0 += FLUSH) {
-    f32x4_t acc[MT];
-#pragma unroll
-    for (int m = 0; m < MT; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    const int s1 = min(nsteps, s0 + FLUSH);
-    for (int s = s0; s < s1; ++s) {
-      advance();
-      float an[MT], gn = 0.f;
-      if (s + 1 < nsteps) load(p, x, y, an, gn);  // uniform: the whole wave takes it
-      bsum += (double)g;
-#pragma unroll
-      for (int m = 0; m < MT; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], g, acc[m], 0, 0, 0);
-#pragma unroll
-      for (int m = 0; m < MT; ++m) av[m] = an[m];
-      g = gn;
-    }
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) accd[m][r] += (double)acc[m][r];
-  }
-  // C layout: register r of lane l = row 4 (l >> 4) + r of the tile, column l & 15; waves in order
-  for (int w = 0; w < 4; ++w) {
-    if (wv == w)
-#pragma unroll
-      for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int e = m * 256 + (4 * slot + r) * 16 + row;
-          red[e] = w == 0 ? accd[m][r] : red[e] + accd[m][r];
-        }
-    __syncthreads();
-  }
-  bred[wv][lane] = bsum;
-  __syncthreads();
-  float* pp = part + (long long)blockIdx.x * (NW + CO);
-  for (int e = threadIdx.x; e < MT * 256; e += 256) {
-    const int m = e >> 8, rr = (e >> 4) & 15, cc = e & 15;
-    const int tap = m * TPM + rr / CI;
-    if (tap >= 9 || cc >= CO) continue;
-    pp[(tap * CI + rr % CI) * CO + cc] = (float)red[e];
-  }
-  if (threadIdx.x < CO) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) v += bred[w][16 * s + threadIdx.x];
-    pp[NW + threadIdx.x] = (float)v;
-  }
-}
-
-// Forward (FWD) and data gradient (!FWD) as pixel-tile GEMMs: out[p][n] = sum_{tap, c} X[p + off][c] *
-// Wk[tap][c][n], K = 9 KC, N = NC.  FWD: X = act(in), KC = CI, NC = CO, off = +tap, Wk = w, C starts at
-// the bias, + res.  !FWD: X = dout, KC = CO, NC = CI, off = -tap, Wk[tap][c][n] = w[tap][n][c], C starts
-// at 0, * [mask > 0] + dres.  A lane loads float4s: lane group g = l >> 4 takes tap TPG-group member
-// g / (KC / 4) and channels 4 (g % (KC / 4)) .. + 3, element j of them feeding k-step j (TPG = 16 / KC taps
-// per load round).  The B fragments (one weight per k-step) stay in VGPRs; each wave runs TW 16-pixel
-// tiles side by side (independent accumulators) over the block's 64 TW consecutive pixels.  Images
-// [0, B1) use (w_a, bias_a), [B1, B) (w_b, bias_b): separate blocks, as conv_fwd_kernel.
-template <int KC, int NC, bool FWD, bool RELU_IN, bool ADD_RES, int TW>
-__global__ __launch_bounds__(256) void conv_mfma_kernel(const float* __restrict__ X, const float* __restrict__ w_a,
-                                                        const float* __restrict__ bias_a, const float* __restrict__ w_b,
-                                                        const float* __restrict__ bias_b, const float* __restrict__ mask,
-                                                        const float* __restrict__ res, float* __restrict__ out, int B,
-                                                        int B1, int H, int W) {
-  constexpr int CG4 = KC / 4, TPG = 4 / CG4, ROUNDS = (9 + TPG - 1) / TPG, NK = ROUNDS * 4;
-  constexpr int PB = 4 * 16 * TW;  // pixels per block
-  static_assert(KC == 4 || KC == 8 || KC == 16, "KC");
-  static_assert(NC == 4 || NC == 8 || NC == 16, "NC");
-  const int n1 = B1 * H * W, nb1 = (n1 + PB - 1) / PB;
-  const bool second = (int)blockIdx.x >= nb1;
-  const int base = second ? n1 + ((int)blockIdx.x - nb1) * PB : (int)blockIdx.x * PB;
-  const int end = second ? B * H * W : n1;
-  const float* __restrict__ w = second ? w_b : w_a;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int col = lane & 15, g = lane >> 4;
-  const int tg = g / CG4, c4 = 4 * (g % CG4);
-  float bw[NK];
-#pragma unroll
-  for (int r = 0; r < ROUNDS; ++r) {
-    const int tap = r * TPG + tg;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float v = 0.f;
-      if (tap < 9 && col < NC) {
-        const int c = c4 + j;
-        v = FWD ? w[(tap * KC + c) * NC + col] : w[(tap * NC + col) * KC + c];
-      }
-      bw[r * 4 + j] = v;
-    }
-  }
-  const float b0 = (FWD && col < NC) ? (second ? bias_b : bias_a)[col] : 0.f;
-  f32x4_t acc[TW];
-  int px[TW], xs[TW], ys[TW];
-  const int p0 = base + wv * 16 * TW;
-#pragma unroll
-  for (int t = 0; t < TW; ++t) {
-    acc[t] = f32x4_t{b0, b0, b0, b0};
-    px[t] = p0 + 16 * t + col;
-    xs[t] = px[t] % W;
-    ys[t] = (px[t] / W) % H;
-  }
-#pragma unroll
-  for (int r = 0; r < ROUNDS; ++r) {
-    const int tap = r * TPG + tg;
-    const int dy = FWD ? tap / 3 - 1 : 1 - tap / 3, dx = FWD ? tap % 3 - 1 : 1 - tap % 3;
-    float4 a[TW];
-#pragma unroll
-    for (int t = 0; t < TW; ++t) {  // unconditional loads from clamped addresses, values selected after
-      const int yy = ys[t] + dy, xx = xs[t] + dx;
-      const bool ok = tap < 9 && px[t] < end && yy >= 0 && yy < H && xx >= 0 && xx < W;
-      const int q = ok ? px[t] + dy * W + dx : base;
-      const float4 v = *reinterpret_cast<const float4*>(X + (long long)q * KC + c4);
-      a[t].x = ok ? (RELU_IN ? fmaxf(v.x, 0.f) : v.x) : 0.f;
-      a[t].y = ok ? (RELU_IN ? fmaxf(v.y, 0.f) : v.y) : 0.f;
-      a[t].z = ok ? (RELU_IN ? fmaxf(v.z, 0.f) : v.z) : 0.f;
-      a[t].w = ok ? (RELU_IN ? fmaxf(v.w, 0.f) : v.w) : 0.f;
-    }
-#pragma unroll
-    for (int t = 0; t < TW; ++t) {
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].x, bw[r * 4 + 0], acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].y, bw[r * 4 + 1], acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].z, bw[r * 4 + 2], acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t].w, bw[r * 4 + 3], acc[t], 0, 0, 0);
-    }
-  }
-  if (col >= NC) return;
-#pragma unroll
-  for (int t = 0; t < TW; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int p = p0 + 16 * t + 4 * g + r;
-      if (p >= end) continue;
-      const long long o = (long long)p * NC + col;
-      float v = acc[t][r];
-      if (!FWD && mask != nullptr) v = mask[o] > 0.f ? v : 0.f;
-      if (ADD_RES) v += res[o];
-      out[o] = v;
-    }
 }
 
 // dw[e] / db[e - nw] = sum_g part[g][e] (e < n): block of 16 entries x 16 lane groups over g
@@ -1782,31 +1572,13 @@ bool conv_supported(int ci, int co) {
   return false;
 }
 
-// channels per lane (measured, rocprofv3 per-kernel sums): the forward keeps every output channel
-// of a pixel in one lane (splitting re-reads the input patch per group) while the launch has enough
-// waves to hide its latency; the data gradient splits 16 input channels into groups of 4 (4x the
-// waves for the same dout reads, 1.4x faster there).  g_drq_fwd_g / g_drq_bwd_g > 0 force a group
-// (experiments, mtsac_debug_drq_groups).
-int g_drq_fwd_g = 0, g_drq_bwd_g = 0;
-static int conv_fwd_group(int co, long long npix) {
-  if (g_drq_fwd_g > 0 && co % g_drq_fwd_g == 0) return g_drq_fwd_g;
-  return co;
+ConvSwitches& conv_switches() {
+  static ConvSwitches sw = [] {  // MTSAC_DRQ_LEGACY=mask in the environment: the legacy mask's default (A/B runs)
+    const char* e = getenv("MTSAC_DRQ_LEGACY");
+    return ConvSwitches{0, 0, e ? (atoi(e) & 63) : 0, 0};
+  }();
+  return sw;
 }
-static int conv_bwd_group(int ci) {
-  if (g_drq_bwd_g > 0 && ci % g_drq_bwd_g == 0) return g_drq_bwd_g;
-  return ci == 16 ? 4 : ci;
-}
-
-// f32-MFMA convolutions (bit 1 forward, 2 data grad, 4 weight grad); the VALU kernels otherwise
-// Measured, not kept (profiles/r4c_*, r4d_*: batch 256, 303-395 vs 494 DrQ steps/s): the f32 MFMA has
-// the packed-FMA rate, so it can only win on operand delivery, and these kernels -- operands one fp32
-// per lane straight from L1/L2, 16-column tiles half empty at 8 channels -- lose to the VALU kernels'
-// scalar-operand FMAs (weight grads 2-3x slower, forwards 1.2-2x).  Opt-in experiments only.
-int g_drq_mfma = [] {
-  const char* e = getenv("MTSAC_DRQ_MFMA");
-  return e ? (atoi(e) & 7) : 0;
-}();
-constexpr int MFMA_TW = 4;  // 16-pixel tiles per wave of conv_mfma_kernel
 
 // Row-tile forward / data-gradient geometry (conv_rows_kernel): for NG = 1, 2, 4 output-channel groups
 // (CG = KO / NG >= 4 channels a lane) a tile holds up to 256 / NG pixels; R = the rows that fit,
@@ -1836,11 +1608,6 @@ static ConvGeo conv_geo(int H, int W, int KI, int KO, int* ng_out) {
   best.magic2 = (unsigned)((0x100000000ULL + (unsigned)W + 1) / (unsigned)(W + 2));
   return best;
 }
-// a forced channel group (mtsac_debug_drq_groups), the MFMA experiment or the legacy mask selects the
-// one-lane-per-pixel kernels
-static bool conv_rows_on(int ng, int forced_group, int bit) {
-  return ng > 0 && forced_group == 0 && !(g_drq_mfma & bit) && !(g_drq_legacy & bit);
-}
 
 // split2h MFMA geometry (conv_h2_kernel): the tallest balanced row tile whose two fp16 planes fit
 // CH_LDS (the staging slots then fit too); R = 0 (the VALU kernels) for W < 2 or too wide a row
@@ -1855,236 +1622,8 @@ static ConvGeo conv_h2_geo(int H, int W, int KI) {
   g.magic2 = (unsigned)((0x100000000ULL + (unsigned)W + 1) / (unsigned)(W + 2));
   return g;
 }
-// the split2h MFMA convs (legacy bit 16: the VALU kernels).  Measured per shape (batch 256,
-// profiles/r6w_drq_h2/conv_bench.txt, us per launch, split2h vs the VALU choice): they win with 16
-// input channels on the small images (forward 21 x 21: 27.3 vs 30.7, 11 x 11: 9.5 vs 9.9; data grad
-// 11.9 vs 14.0, 7.2 vs 8.0) and lose elsewhere (42 x 42 8 -> 8 forward 46.5 vs 30.1; the data grads
-// at 42 and 84: 22-58 vs 14-32): the per-block weight gather and split and the staging's max
-// reduction cost more than the MFMAs save there.  They run for KI = 16, W <= 32.
-static bool conv_h2_on(const ConvGeo& g, int KI, int bit) {
-  const bool shape = (KI == 16 && g.W <= 32) || (g_drq_legacy & 32);  // bit 32: every supported shape
-  return g.R > 0 && shape && !(g_drq_legacy & 16) && !(g_drq_legacy & bit) && !(g_drq_mfma & bit);
-}
 
-// What a forward / data-gradient launcher runs under the current masks, decided in one place (the
-// launchers and mtsac_debug_drq_conv_path both ask here): family 0 one lane per pixel, 1 row tiles,
-// 2 split2h MFMA, 3 f32 MFMA; geo / ng of the tiled families, G channels per lane of the pixel
-// kernels, the grid (gx, gy)
-struct ConvSel {
-  int family, ng, G;
-  ConvGeo geo;
-  unsigned gx, gy;
-};
-static ConvSel conv_fwd_sel(int B, int B1, int H, int W, int ci, int co) {
-  ConvSel s{};
-  s.gy = 1;
-  const long long npix = (long long)B * H * W, n1 = (long long)B1 * H * W;
-  if (ci >= 8 && g_drq_fwd_g == 0) {
-    s.geo = conv_h2_geo(H, W, ci);
-    if (conv_h2_on(s.geo, ci, 1)) {
-      s.family = 2;
-      s.gx = (unsigned)(B * s.geo.n);
-      return s;
-    }
-  }
-  s.geo = conv_geo(H, W, ci, co, &s.ng);
-  if (conv_rows_on(s.ng, g_drq_fwd_g, 1)) {
-    s.family = 1;
-    s.gx = (unsigned)(B * s.geo.n);
-    return s;
-  }
-  if (g_drq_mfma & 1) {
-    constexpr int PB = 64 * MFMA_TW;
-    s.family = 3;
-    s.gx = (unsigned)((n1 + PB - 1) / PB + (npix - n1 + PB - 1) / PB);
-    return s;
-  }
-  s.G = conv_fwd_group(co, npix);
-  s.gx = blocks(n1) + blocks(npix - n1);
-  s.gy = (unsigned)(co / s.G);
-  return s;
-}
-static ConvSel conv_bwd_sel(int B, int H, int W, int ci, int co) {
-  ConvSel s{};
-  s.gy = 1;
-  const long long npix = (long long)B * H * W;
-  if (co >= 8 && g_drq_bwd_g == 0) {  // the transposed conv on split2h MFMA: KI = co, KO = ci
-    s.geo = conv_h2_geo(H, W, co);
-    if (conv_h2_on(s.geo, co, 2)) {
-      s.family = 2;
-      s.gx = (unsigned)(B * s.geo.n);
-      return s;
-    }
-  }
-  s.geo = conv_geo(H, W, co, ci, &s.ng);
-  // measured (profiles/r6o_drq/conv_bench.txt): the row-tile data grad wins with 16 dout channels
-  // from 21 x 21 up (21 x 21: 13.6 vs 28.2 us, 42 x 42 8 -> 16: 25.0 vs 27.9) and loses with 8 (42 x 42:
-  // 15.2 vs 13.9) and at 11 x 11 (8.5 vs 7.9): it runs for co = 16, W >= 16
-  if (((co >= 16 && W >= 16) || (g_drq_legacy & 8)) && conv_rows_on(s.ng, g_drq_bwd_g, 2)) {
-    s.family = 1;
-    s.gx = (unsigned)(B * s.geo.n);
-    return s;
-  }
-  if (g_drq_mfma & 2) {
-    constexpr int PB = 64 * MFMA_TW;
-    s.family = 3;
-    s.gx = (unsigned)((npix + PB - 1) / PB);
-    return s;
-  }
-  s.G = conv_bwd_group(ci);
-  s.gx = blocks(npix);
-  s.gy = (unsigned)(ci / s.G);
-  return s;
-}
-
-void conv_fwd(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
-              int ci, int co, bool relu_in, hipStream_t st, const float* w2, const float* bias2, int B1) {
-  if (w2 == nullptr || B1 < 0 || B1 > B) {  // one parameter set
-    w2 = w;
-    bias2 = bias;
-    B1 = B;
-  }
-  const ConvSel sel = conv_fwd_sel(B, B1, H, W, ci, co);
-  const ConvGeo geo = sel.geo;
-  const int G = sel.G, ng = sel.ng;
-  {
-    if (sel.family == 2) {
-      const dim3 gr(sel.gx), tb(256);
-#define C_FH(a, b)                                                                                                   \
-  if (ci == a && co == b) {                                                                                          \
-    if (relu_in && res) hipLaunchKernelGGL((conv_h2_kernel<a, b, true, true, false, true>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-    else if (relu_in) hipLaunchKernelGGL((conv_h2_kernel<a, b, true, true, false, false>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-    else if (res) hipLaunchKernelGGL((conv_h2_kernel<a, b, true, false, false, true>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-    else hipLaunchKernelGGL((conv_h2_kernel<a, b, true, false, false, false>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-    return;                                                                                                          \
-  }
-      C_FH(8, 8) C_FH(8, 16) C_FH(16, 16)
-#undef C_FH
-    }
-  }
-  {
-    if (sel.family == 1) {
-      const dim3 gr(sel.gx), tb(256);
-#define C_FR_G(a, b, cg)                                                                                            \
-  if (relu_in && res) hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, true, false, true>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-  else if (relu_in) hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, true, false, false>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-  else if (res) hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, false, false, true>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo); \
-  else hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, false, false, false>), gr, tb, 0, st, in, w, bias, w2, bias2, B1, nullptr, res, out, geo);
-#define C_FR(a, b)                                   \
-  if (ci == a && co == b) {                          \
-    if (ng == 1) { C_FR_G(a, b, b) }                 \
-    else if (ng == 2) { C_FR_G(a, b, b / 2) }        \
-    else if constexpr (b >= 16) { C_FR_G(a, b, b / 4) } \
-    return;                                          \
-  }
-      CONV_CASES(C_FR)
-#undef C_FR
-#undef C_FR_G
-    }
-  }
-  if (sel.family == 3) {
-    const dim3 gm(sel.gx), tm(256);
-#define C_FWDM(a, b)                                                                                                 \
-  if (ci == a && co == b) {                                                                                          \
-    if (relu_in && res) hipLaunchKernelGGL((conv_mfma_kernel<a, b, true, true, true, MFMA_TW>), gm, tm, 0, st, in, w, bias, w2, bias2, nullptr, res, out, B, B1, H, W); \
-    else if (relu_in) hipLaunchKernelGGL((conv_mfma_kernel<a, b, true, true, false, MFMA_TW>), gm, tm, 0, st, in, w, bias, w2, bias2, nullptr, res, out, B, B1, H, W); \
-    else if (res) hipLaunchKernelGGL((conv_mfma_kernel<a, b, true, false, true, MFMA_TW>), gm, tm, 0, st, in, w, bias, w2, bias2, nullptr, res, out, B, B1, H, W); \
-    else hipLaunchKernelGGL((conv_mfma_kernel<a, b, true, false, false, MFMA_TW>), gm, tm, 0, st, in, w, bias, w2, bias2, nullptr, res, out, B, B1, H, W); \
-    return;                                                                                                          \
-  }
-    CONV_CASES(C_FWDM)
-#undef C_FWDM
-  }
-  const dim3 g(sel.gx, sel.gy), t(256);
-#define C_FWD_G(a, b, cg)                                                                                           \
-  if (relu_in && res) hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, true, true>), g, t, 0, st, in, w, bias, w2, bias2, res, out, B, B1, H, W); \
-  else if (relu_in) hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, true, false>), g, t, 0, st, in, w, bias, w2, bias2, res, out, B, B1, H, W); \
-  else if (res) hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, false, true>), g, t, 0, st, in, w, bias, w2, bias2, res, out, B, B1, H, W); \
-  else hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, false, false>), g, t, 0, st, in, w, bias, w2, bias2, res, out, B, B1, H, W);
-#define C_FWD(a, b)                   \
-  if (ci == a && co == b) {           \
-    if (G == b) { C_FWD_G(a, b, b) }  \
-    else if (G == 8) { C_FWD_G(a, b, 8) } \
-    else { C_FWD_G(a, b, 4) }         \
-    return;                           \
-  }
-  CONV_CASES(C_FWD)
-#undef C_FWD
-#undef C_FWD_G
-}
-
-void conv_bwd_data(const float* dout, const float* w, const float* mask, const float* dres, float* din, int B, int H,
-                   int W, int ci, int co, hipStream_t st) {
-  const ConvSel sel = conv_bwd_sel(B, H, W, ci, co);
-  const ConvGeo geo = sel.geo;
-  const int G = sel.G, ng = sel.ng;
-  {  // the transposed conv on split2h MFMA: KI = co, KO = ci
-    if (sel.family == 2) {
-      const dim3 gr(sel.gx), tb(256);
-#define C_BH(a, b)                                                                                                   \
-  if (ci == a && co == b) {                                                                                          \
-    if (mask && dres) hipLaunchKernelGGL((conv_h2_kernel<b, a, false, false, true, true>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-    else if (mask) hipLaunchKernelGGL((conv_h2_kernel<b, a, false, false, true, false>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-    else if (dres) hipLaunchKernelGGL((conv_h2_kernel<b, a, false, false, false, true>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-    else hipLaunchKernelGGL((conv_h2_kernel<b, a, false, false, false, false>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-    return;                                                                                                          \
-  }
-      C_BH(4, 8) C_BH(8, 8) C_BH(8, 16) C_BH(16, 16)
-#undef C_BH
-    }
-  }
-  {  // the transposed conv: KI = co (dout channels), KO = ci
-    if (sel.family == 1) {
-      const dim3 gr(sel.gx), tb(256);
-#define C_BR_G(a, b, cg)                                                                                            \
-  if (mask && dres) hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, true, true>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-  else if (mask) hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, true, false>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-  else if (dres) hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, false, true>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo); \
-  else hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, false, false>), gr, tb, 0, st, dout, w, nullptr, w, nullptr, B, mask, dres, din, geo);
-#define C_BR(a, b)                                   \
-  if (ci == a && co == b) {                          \
-    if (ng == 1) { C_BR_G(a, b, a) }                 \
-    else if constexpr (a >= 8) {                     \
-      if (ng == 2) { C_BR_G(a, b, a / 2) }           \
-      else if constexpr (a >= 16) { C_BR_G(a, b, a / 4) } \
-    }                                                \
-    return;                                          \
-  }
-      CONV_CASES(C_BR)
-#undef C_BR
-#undef C_BR_G
-    }
-  }
-  if (sel.family == 3) {  // K channels = co, N = ci
-    const dim3 gm(sel.gx), tm(256);
-#define C_BDM(a, b)                                                                                                  \
-  if (ci == a && co == b) {                                                                                          \
-    if (dres) hipLaunchKernelGGL((conv_mfma_kernel<b, a, false, false, true, MFMA_TW>), gm, tm, 0, st, dout, w, nullptr, w, nullptr, mask, dres, din, B, B, H, W); \
-    else hipLaunchKernelGGL((conv_mfma_kernel<b, a, false, false, false, MFMA_TW>), gm, tm, 0, st, dout, w, nullptr, w, nullptr, mask, dres, din, B, B, H, W); \
-    return;                                                                                                          \
-  }
-    CONV_CASES(C_BDM)
-#undef C_BDM
-  }
-  const dim3 g(sel.gx, sel.gy), t(256);
-#define C_BD_G(a, b, cg)                                                                                            \
-  if (mask && dres) hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, true, true>), g, t, 0, st, dout, w, mask, dres, din, B, H, W); \
-  else if (mask) hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, true, false>), g, t, 0, st, dout, w, mask, dres, din, B, H, W); \
-  else if (dres) hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, false, true>), g, t, 0, st, dout, w, mask, dres, din, B, H, W); \
-  else hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, false, false>), g, t, 0, st, dout, w, mask, dres, din, B, H, W);
-#define C_BD(a, b)                   \
-  if (ci == a && co == b) {          \
-    if (G == a) { C_BD_G(a, b, a) }  \
-    else if (G == 8) { if constexpr (a >= 8) { C_BD_G(a, b, 8) } } \
-    else { C_BD_G(a, b, 4) }         \
-    return;                          \
-  }
-  CONV_CASES(C_BD)
-#undef C_BD
-#undef C_BD_G
-}
-
-// Row-tile weight gradients (conv_wgrad_rows_kernel): the tallest tile whose staging fits the
+// Row-tile weight-gradient geometry (conv_wgrad_rows_kernel): the tallest tile whose staging fits the
 // per-thread slots and the kernel's LDS, shortened until the batch gives >= 512 tiles (two blocks
 // per CU), then balanced (equal row counts per image); R = 0 when even one row does not fit (very wide
 // images) or W < 2 (the magic division), where the im2col kernel runs instead.
@@ -2094,7 +1633,6 @@ static int wg_lds_floats(int ci, int co) {
 #undef C_WL
   return 0;
 }
-int g_drq_wg_blocks = 0;  // > 0: the row-tile weight grad's grid cap (mtsac_debug_drq_wgrad_blocks)
 static WgGeo wgrad_geo(int B, int H, int W, int ci, int co) {
   WgGeo g{H, W, 0, (W + 2) * ci + 4, 0, 0u};
   const int slots = 8 * 256, ldsf = wg_lds_floats(ci, co);
@@ -2110,78 +1648,220 @@ static WgGeo wgrad_geo(int B, int H, int W, int ci, int co) {
   g.magic = (unsigned)((0x100000000ULL + (unsigned)W - 1) / (unsigned)W);
   return g;
 }
-int g_drq_legacy = [] {  // MTSAC_DRQ_LEGACY=mask in the environment: the same selection (A/B runs)
-  const char* e = getenv("MTSAC_DRQ_LEGACY");
-  return e ? (atoi(e) & 63) : 0;
-}();
-// Measured per shape (profiles/r6l_drq/conv_bench.txt, batch 256): the row-tile weight grad wins from
-// 21 x 21 up (84 x 84 4 -> 8: 41.5 vs 90.1 us) and loses at 11 x 11 (15.5 vs 9.7: one tile per block,
-// where the pixel-group tree is most of the work), so it runs for W >= 16
-static bool wgrad_rows(const WgGeo& g) {
-  return g.R > 0 && (g.W >= 16 || (g_drq_legacy & 8)) && !(g_drq_mfma & 4) && !(g_drq_legacy & 4);
-}
-static int wgrad_cap(const WgGeo& g) {  // grid cap: 1024 at 84 x 84 (35.6 vs 41.5 us at 512), else 512
-  return g_drq_wg_blocks > 0 ? g_drq_wg_blocks : (g.W >= 64 ? 1024 : 512);
-}
 
-// im2col kernel: enough 64-pixel tiles in flight per CU to cover the staging loads' latency (the
-// partials' reduction is cheap next to them); the MFMA experiment takes chunks of npix / G pixels
-int conv_wgrad_blocks(int B, int H, int W, int ci, int co) {
-  const WgGeo g = wgrad_geo(B, H, W, ci, co);
-  if (wgrad_rows(g)) return std::min(g.tiles, wgrad_cap(g));
-  const long long npix = (long long)B * H * W;
-  return (int)std::min<long long>(2048, std::max<long long>(1, (npix + 63) / 64));
-}
-
-// the weight-grad launcher's choice (family 0 im2col, 1 row tiles, 3 f32 MFMA) and its G blocks
-struct WgSel {
-  int family, G;
-  WgGeo geo;
-};
-static WgSel conv_wgrad_sel(int B, int H, int W, int ci, int co) {
-  WgSel s{};
-  s.geo = wgrad_geo(B, H, W, ci, co);
-  s.G = conv_wgrad_blocks(B, H, W, ci, co);
-  s.family = wgrad_rows(s.geo) ? 1 : (g_drq_mfma & 4) ? 3 : 0;
-  return s;
-}
-
-ConvPath conv_path(int kind, int B, int H, int W, int ci, int co) {
+// What runs for one conv, decided here and nowhere else: the only reader of the switches.
+ConvPlan conv_plan(int kind, int B, int H, int W, int ci, int co) {
+  const ConvSwitches sw = conv_switches();
+  ConvPlan p{};
+  p.kind = kind;
+  p.H = H;
+  p.W = W;
+  p.ci = ci;
+  p.co = co;
   if (kind == 2) {
-    const WgSel s = conv_wgrad_sel(B, H, W, ci, co);
-    if (s.family == 1) return ConvPath{1, s.geo.R, s.geo.tiles / B, s.G};
-    return ConvPath{s.family, 0, 0, s.G};
+    p.B = B;
+    p.wg = wgrad_geo(B, H, W, ci, co);
+    // Measured per shape (profiles/r6l_drq/conv_bench.txt, batch 256): the row-tile weight grad wins
+    // from 21 x 21 up (84 x 84 4 -> 8: 41.5 vs 90.1 us) and loses at 11 x 11 (15.5 vs 9.7: one tile per
+    // block, where the pixel-group tree is most of the work), so it runs for W >= 16
+    if (p.wg.R > 0 && (W >= 16 || (sw.legacy & 8)) && !(sw.legacy & 4)) {
+      p.family = 1;  // grid cap: 1024 at 84 x 84 (35.6 vs 41.5 us at 512), else 512
+      p.rows = std::min(p.wg.tiles, sw.wg_blocks > 0 ? sw.wg_blocks : (W >= 64 ? 1024 : 512));
+    } else {  // im2col: enough 64-pixel tiles in flight per CU to cover the staging loads' latency
+      const long long npix = (long long)B * H * W;  // (the partials' reduction is cheap next to them)
+      p.rows = (int)std::min<long long>(2048, std::max<long long>(1, (npix + 63) / 64));
+    }
+    return p;
   }
-  const ConvSel s = kind == 0 ? conv_fwd_sel(B, B, H, W, ci, co) : conv_bwd_sel(B, H, W, ci, co);
-  const bool tiled = s.family == 1 || s.family == 2;
-  return ConvPath{s.family, tiled ? s.geo.R : 0, tiled ? s.geo.n : 0, (int)(s.gx * s.gy)};
+  // the forward sums KI = ci channels into KO = co; the data gradient is the transposed conv
+  const bool fwd = kind == 0;
+  const int KI = fwd ? ci : co, KO = fwd ? co : ci;
+  const int bit = fwd ? 1 : 2, forced = fwd ? sw.fwd_g : sw.bwd_g;  // a forced group: the pixel kernels
+  // the split2h MFMA convs (legacy bit 16: the VALU kernels).  Measured per shape (batch 256,
+  // profiles/r6w_drq_h2/conv_bench.txt, us per launch, split2h vs the VALU choice): they win with 16
+  // input channels on the small images (forward 21 x 21: 27.3 vs 30.7, 11 x 11: 9.5 vs 9.9; data grad
+  // 11.9 vs 14.0, 7.2 vs 8.0) and lose elsewhere (42 x 42 8 -> 8 forward 46.5 vs 30.1; the data grads
+  // at 42 and 84: 22-58 vs 14-32): the per-block weight gather and split and the staging's max
+  // reduction cost more than the MFMAs save there.  They run for KI = 16, W <= 32 (bit 32: every
+  // supported shape).
+  if (KI >= 8 && forced == 0) {
+    p.geo = conv_h2_geo(H, W, KI);
+    const bool shape = (KI == 16 && W <= 32) || (sw.legacy & 32);
+    if (p.geo.R > 0 && shape && !(sw.legacy & 16) && !(sw.legacy & bit)) {
+      p.family = 2;
+      return p;
+    }
+  }
+  p.geo = conv_geo(H, W, KI, KO, &p.ng);
+  // measured (profiles/r6o_drq/conv_bench.txt): the row-tile data grad wins with 16 dout channels
+  // from 21 x 21 up (21 x 21: 13.6 vs 28.2 us, 42 x 42 8 -> 16: 25.0 vs 27.9) and loses with 8 (42 x 42:
+  // 15.2 vs 13.9) and at 11 x 11 (8.5 vs 7.9): it runs for co = 16, W >= 16; the forward's at every shape
+  const bool shape = fwd || (co >= 16 && W >= 16) || (sw.legacy & 8);
+  if (shape && p.ng > 0 && forced == 0 && !(sw.legacy & bit)) {
+    p.family = 1;
+    return p;
+  }
+  // channels per lane (measured, rocprofv3 per-kernel sums): the forward keeps every output channel
+  // of a pixel in one lane (splitting re-reads the input patch per group) while the launch has enough
+  // waves to hide its latency; the data gradient splits 16 input channels into groups of 4 (4x the
+  // waves for the same dout reads, 1.4x faster there)
+  p.G = forced > 0 && KO % forced == 0 ? forced : (!fwd && ci == 16) ? 4 : KO;
+  return p;
 }
 
-void conv_wgrad(const float* in, const float* dout, float* part, float* dw, float* db, int B, int H, int W, int ci,
-                int co, bool relu_in, hipStream_t st, bool defer_sum) {
-  const long long npix = (long long)B * H * W;
-  const WgSel sel = conv_wgrad_sel(B, H, W, ci, co);
-  const WgGeo geo = sel.geo;
-  const bool rows = sel.family == 1;
-  const int G = sel.G;
-  const int chunk = (int)(((npix + G - 1) / G + 15) / 16 * 16);
-#define C_WG(a, b)                                                                                             \
-  if (ci == a && co == b) {                                                                                    \
-    if (rows) {                                                                                                \
-      if (relu_in) hipLaunchKernelGGL((conv_wgrad_rows_kernel<a, b, true>), dim3(G), dim3(256), 0, st, in, dout, part, geo); \
-      else hipLaunchKernelGGL((conv_wgrad_rows_kernel<a, b, false>), dim3(G), dim3(256), 0, st, in, dout, part, geo);      \
-    } else if (sel.family == 3) {                                                                              \
-      if (relu_in) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<a, b, true>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W, chunk); \
-      else hipLaunchKernelGGL((conv_wgrad_mfma_kernel<a, b, false>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W, chunk);      \
-    } else if (relu_in) hipLaunchKernelGGL((conv_wgrad_kernel<a, b, true>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W); \
-    else hipLaunchKernelGGL((conv_wgrad_kernel<a, b, false>), dim3(G), dim3(256), 0, st, in, dout, part, B, H, W);        \
+// grid of a forward / data-gradient launch over B images, [0, B1) on the first parameter set (the
+// pixel kernels give each set its own blocks)
+static dim3 conv_grid(const ConvPlan& p, int B, int B1) {
+  if (p.family != 0) return dim3((unsigned)(B * p.geo.n));
+  const long long n1 = (long long)B1 * p.H * p.W, npix = (long long)B * p.H * p.W;
+  return dim3(blocks(n1) + blocks(npix - n1), (unsigned)((p.kind == 0 ? p.co : p.ci) / p.G));
+}
+
+int conv_blocks(const ConvPlan& p, int B) {
+  if (p.kind == 2) return p.rows;
+  const dim3 g = conv_grid(p, B, B);
+  return (int)(g.x * g.y);
+}
+
+// f(std::bool_constant<a>, std::bool_constant<b>): a launcher's two runtime flags as template
+// arguments, so each family's launch is written once
+template <class F>
+static void with_bools(bool a, bool b, F&& f) {
+  if (a && b) f(std::true_type{}, std::true_type{});
+  else if (a) f(std::true_type{}, std::false_type{});
+  else if (b) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+#define BV(x) decltype(x)::value
+
+void conv_fwd(const ConvPlan& pl, const float* in, const float* w, const float* bias, const float* res, float* out,
+              int B, bool relu_in, hipStream_t st, const float* w2, const float* bias2, int B1) {
+  if (w2 == nullptr || B1 < 0 || B1 > B) {  // one parameter set
+    w2 = w;
+    bias2 = bias;
+    B1 = B;
   }
+  const int H = pl.H, W = pl.W, ci = pl.ci, co = pl.co, G = pl.G, ng = pl.ng;
+  const ConvGeo geo = pl.geo;
+  const dim3 g = conv_grid(pl, B, B1), t(256);
+  if (pl.family == 2) {
+#define C_FH(a, b)                                                                                                 \
+  if (ci == a && co == b) {                                                                                        \
+    with_bools(relu_in, res != nullptr, [&](auto relu, auto add) {                                                 \
+      hipLaunchKernelGGL((conv_h2_kernel<a, b, true, BV(relu), false, BV(add)>), g, t, 0, st, in, w, bias, w2,     \
+                         bias2, B1, nullptr, res, out, geo);                                                       \
+    });                                                                                                            \
+    return;                                                                                                        \
+  }
+    C_FH(8, 8) C_FH(8, 16) C_FH(16, 16)
+#undef C_FH
+  }
+  if (pl.family == 1) {
+#define C_FR_G(a, b, cg)                                                                                           \
+  with_bools(relu_in, res != nullptr, [&](auto relu, auto add) {                                                   \
+    hipLaunchKernelGGL((conv_rows_kernel<a, b, cg, true, BV(relu), false, BV(add)>), g, t, 0, st, in, w, bias, w2, \
+                       bias2, B1, nullptr, res, out, geo);                                                         \
+  });
+#define C_FR(a, b)                                      \
+  if (ci == a && co == b) {                             \
+    if (ng == 1) { C_FR_G(a, b, b) }                    \
+    else if (ng == 2) { C_FR_G(a, b, b / 2) }           \
+    else if constexpr (b >= 16) { C_FR_G(a, b, b / 4) } \
+    return;                                             \
+  }
+    CONV_CASES(C_FR)
+#undef C_FR
+#undef C_FR_G
+  }
+#define C_FWD_G(a, b, cg)                                                                                       \
+  with_bools(relu_in, res != nullptr, [&](auto relu, auto add) {                                                \
+    hipLaunchKernelGGL((conv_fwd_kernel<a, b, cg, BV(relu), BV(add)>), g, t, 0, st, in, w, bias, w2, bias2, res, \
+                       out, B, B1, H, W);                                                                       \
+  });
+#define C_FWD(a, b)                       \
+  if (ci == a && co == b) {               \
+    if (G == b) { C_FWD_G(a, b, b) }      \
+    else if (G == 8) { C_FWD_G(a, b, 8) } \
+    else { C_FWD_G(a, b, 4) }             \
+    return;                               \
+  }
+  CONV_CASES(C_FWD)
+#undef C_FWD
+#undef C_FWD_G
+}
+
+void conv_bwd_data(const ConvPlan& pl, const float* dout, const float* w, const float* mask, const float* dres,
+                   float* din, int B, hipStream_t st) {
+  const int H = pl.H, W = pl.W, ci = pl.ci, co = pl.co, G = pl.G, ng = pl.ng;
+  const ConvGeo geo = pl.geo;
+  const dim3 g = conv_grid(pl, B, B), t(256);
+  if (pl.family == 2) {  // the transposed conv on split2h MFMA: KI = co, KO = ci
+#define C_BH(a, b)                                                                                                 \
+  if (ci == a && co == b) {                                                                                        \
+    with_bools(mask != nullptr, dres != nullptr, [&](auto msk, auto add) {                                         \
+      hipLaunchKernelGGL((conv_h2_kernel<b, a, false, false, BV(msk), BV(add)>), g, t, 0, st, dout, w, nullptr, w, \
+                         nullptr, B, mask, dres, din, geo);                                                        \
+    });                                                                                                            \
+    return;                                                                                                        \
+  }
+    CONV_CASES(C_BH)
+#undef C_BH
+  }
+  if (pl.family == 1) {  // the transposed conv: KI = co (dout channels), KO = ci
+#define C_BR_G(a, b, cg)                                                                                           \
+  with_bools(mask != nullptr, dres != nullptr, [&](auto msk, auto add) {                                           \
+    hipLaunchKernelGGL((conv_rows_kernel<b, a, cg, false, false, BV(msk), BV(add)>), g, t, 0, st, dout, w, nullptr, \
+                       w, nullptr, B, mask, dres, din, geo);                                                       \
+  });
+#define C_BR(a, b)                                        \
+  if (ci == a && co == b) {                               \
+    if (ng == 1) { C_BR_G(a, b, a) }                      \
+    else if constexpr (a >= 8) {                          \
+      if (ng == 2) { C_BR_G(a, b, a / 2) }                \
+      else if constexpr (a >= 16) { C_BR_G(a, b, a / 4) } \
+    }                                                     \
+    return;                                               \
+  }
+    CONV_CASES(C_BR)
+#undef C_BR
+#undef C_BR_G
+  }
+#define C_BD_G(a, b, cg)                                                                                        \
+  with_bools(mask != nullptr, dres != nullptr, [&](auto msk, auto add) {                                        \
+    hipLaunchKernelGGL((conv_bwd_data_kernel<a, b, cg, BV(msk), BV(add)>), g, t, 0, st, dout, w, mask, dres, din, \
+                       B, H, W);                                                                                \
+  });
+#define C_BD(a, b)                                                 \
+  if (ci == a && co == b) {                                        \
+    if (G == a) { C_BD_G(a, b, a) }                                \
+    else if (G == 8) { if constexpr (a >= 8) { C_BD_G(a, b, 8) } } \
+    else { C_BD_G(a, b, 4) }                                       \
+    return;                                                        \
+  }
+  CONV_CASES(C_BD)
+#undef C_BD
+#undef C_BD_G
+}
+
+void conv_wgrad(const ConvPlan& pl, const float* in, const float* dout, float* part, float* dw, float* db,
+                bool relu_in, hipStream_t st, bool defer_sum) {
+  const int ci = pl.ci, co = pl.co, G = pl.rows;
+  const dim3 g(G), t(256);
+#define C_WG(a, b)                                                                                              \
+  if (ci == a && co == b)                                                                                       \
+    with_bools(pl.family == 1, relu_in, [&](auto rows, auto relu) {                                             \
+      if constexpr (BV(rows))                                                                                   \
+        hipLaunchKernelGGL((conv_wgrad_rows_kernel<a, b, BV(relu)>), g, t, 0, st, in, dout, part, pl.wg);       \
+      else                                                                                                      \
+        hipLaunchKernelGGL((conv_wgrad_kernel<a, b, BV(relu)>), g, t, 0, st, in, dout, part, pl.B, pl.H, pl.W); \
+    });
   CONV_CASES(C_WG)
 #undef C_WG
   if (defer_sum) return;  // summed with the other convs' partials by sum_parts_multi
   const int nw = 9 * ci * co, n = nw + co;
   hipLaunchKernelGGL(sum_parts_kernel, dim3((n + 15) / 16), dim3(256), 0, st, part, G, n, dw, db, nw);
 }
+#undef BV
 
 int sum_parts_blocks(int ci, int co) { return (9 * ci * co + co + 15) / 16; }
 
@@ -2191,8 +1871,8 @@ int sum_parts_blocks(int ci, int co) { return (9 * ci * co + co + 15) / 16; }
 double conv_bench(int kind, int B, int H, int W, int ci, int co, int iters) {
   const long long np = (long long)B * H * W;
   const long long nx = np * (kind == 1 ? co : ci), ny = np * (kind == 1 ? ci : co);
-  const int G = conv_wgrad_blocks(B, H, W, ci, co);
-  const long long nz = kind == 2 ? (long long)G * (9 * ci * co + co) : ny;
+  const ConvPlan pl = conv_plan(kind, B, H, W, ci, co);
+  const long long nz = kind == 2 ? (long long)pl.rows * (9 * ci * co + co) : ny;
   std::vector<float> hx((size_t)std::max({nx, ny, 9LL * ci * co + co}));
   unsigned long long z = 88172645463325252ULL;
   for (float& v : hx) {
@@ -2207,9 +1887,9 @@ double conv_bench(int kind, int B, int H, int W, int ci, int co, int iters) {
   (void)hipMemcpy(y, hx.data(), ny * 4, hipMemcpyHostToDevice);
   (void)hipMemcpy(w, hx.data(), (9LL * ci * co + co) * 4, hipMemcpyHostToDevice);
   auto run = [&] {
-    if (kind == 0) conv_fwd(x, w, w + 9 * ci * co, y, o, B, H, W, ci, co, true, nullptr);
-    else if (kind == 1) conv_bwd_data(x, w, y, y, o, B, H, W, ci, co, nullptr);
-    else conv_wgrad(x, y, o, nullptr, nullptr, B, H, W, ci, co, true, nullptr, true);
+    if (kind == 0) conv_fwd(pl, x, w, w + 9 * ci * co, y, o, B, true, nullptr);
+    else if (kind == 1) conv_bwd_data(pl, x, w, y, y, o, B, nullptr);
+    else conv_wgrad(pl, x, y, o, nullptr, nullptr, true, nullptr, true);
   };
   run();
   hipEvent_t e0, e1;

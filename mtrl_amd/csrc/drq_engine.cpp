@@ -45,6 +45,9 @@ struct Stack {
   unsigned char* arg = nullptr;
   float* c[3] = {};        // block inputs / output, [B][ho][ho][co]
   float* r[2] = {};        // residual blocks' inner pre-activations
+  // what runs for its convs, fixed at create: [0] Conv_0 (hin x hin, ci -> co), [1] the four block
+  // convs (ho x ho, co -> co); the weight-grad plans are for the update's batch
+  drq::ConvPlan fwd[2], bwd[2], wg[2];
 };
 
 }  // namespace
@@ -152,11 +155,11 @@ struct drq_engine {
     const float* x = X;
     for (int s = 0; s < 3; ++s) {
       Stack& k = stk[s];
-      conv_fwd_t(x, P, Q2, k.cw[0], k.cb[0], nullptr, k.conv0, B, B1, k.hin, k.ci, k.co, false);
+      conv_fwd_t(k.fwd[0], x, P, Q2, k.cw[0], k.cb[0], nullptr, k.conv0, B, B1, false);
       drq::maxpool_fwd(k.conv0, k.c[0], k.arg, B, k.hin, k.hin, k.co, st);
       for (int b = 0; b < cfg_blocks(); ++b) {
-        conv_fwd_t(k.c[b], P, Q2, k.cw[1 + 2 * b], k.cb[1 + 2 * b], nullptr, k.r[b], B, B1, k.ho, k.co, k.co, true);
-        conv_fwd_t(k.r[b], P, Q2, k.cw[2 + 2 * b], k.cb[2 + 2 * b], k.c[b], k.c[b + 1], B, B1, k.ho, k.co, k.co, true);
+        conv_fwd_t(k.fwd[1], k.c[b], P, Q2, k.cw[1 + 2 * b], k.cb[1 + 2 * b], nullptr, k.r[b], B, B1, true);
+        conv_fwd_t(k.fwd[1], k.r[b], P, Q2, k.cw[2 + 2 * b], k.cb[2 + 2 * b], k.c[b], k.c[b + 1], B, B1, true);
       }
       x = k.c[2];
     }
@@ -186,9 +189,8 @@ struct drq_engine {
   double t_flops = 0;
   long long t_launches = 0;
   // conv (weights at offset cw, bias at cb) of images [0, B1) at params P and [B1, Bn) at P2
-  void conv_fwd_t(const float* in, const float* P, const float* P2, long long cw, long long cb, const float* res,
-                  float* out, int Bn, int B1, int Hh, int ci, int co, bool relu_in) {
-    const int Ww = Hh;
+  void conv_fwd_t(const drq::ConvPlan& pl, const float* in, const float* P, const float* P2, long long cw,
+                  long long cb, const float* res, float* out, int Bn, int B1, bool relu_in) {
     hipEvent_t a = nullptr, b = nullptr;
     if (timing && count % 8 == 0) {
       while (ev.size() < ev_used + 2) {
@@ -203,10 +205,10 @@ struct drq_engine {
         (void)hipEventRecord(a, st);
       }
     }
-    drq::conv_fwd(in, P + cw, P + cb, res, out, Bn, Hh, Ww, ci, co, relu_in, st, P2 + cw, P2 + cb, B1);
+    drq::conv_fwd(pl, in, P + cw, P + cb, res, out, Bn, relu_in, st, P2 + cw, P2 + cb, B1);
     if (a) {
       (void)hipEventRecord(b, st);
-      t_flops += 2.0 * Bn * Hh * Ww * 9.0 * ci * co;
+      t_flops += 2.0 * Bn * pl.H * pl.W * 9.0 * pl.ci * pl.co;
       ++t_launches;
     }
   }
@@ -397,16 +399,16 @@ struct drq_engine {
       Stack& k = stk[s];
       for (int b = 1; b >= 0; --b) {  // c[b + 1] = conv_k2(relu(r[b])) + c[b], r[b] = conv_k1(relu(c[b]))
         const int k2 = 2 + 2 * b, k1 = 1 + 2 * b;
-        drq::conv_wgrad(k.r[b], dc, wparts[s][k2], g + k.cw[k2], g + k.cb[k2], B, k.ho, k.ho, k.co, k.co, true, st, true);
-        drq::conv_bwd_data(dc, p + k.cw[k2], k.r[b], nullptr, dr, B, k.ho, k.ho, k.co, k.co, st);
-        drq::conv_wgrad(k.c[b], dr, wparts[s][k1], g + k.cw[k1], g + k.cb[k1], B, k.ho, k.ho, k.co, k.co, true, st, true);
-        drq::conv_bwd_data(dr, p + k.cw[k1], k.c[b], dc, dn, B, k.ho, k.ho, k.co, k.co, st);
+        drq::conv_wgrad(k.wg[1], k.r[b], dc, wparts[s][k2], g + k.cw[k2], g + k.cb[k2], true, st, true);
+        drq::conv_bwd_data(k.bwd[1], dc, p + k.cw[k2], k.r[b], nullptr, dr, B, st);
+        drq::conv_wgrad(k.wg[1], k.c[b], dr, wparts[s][k1], g + k.cw[k1], g + k.cb[k1], true, st, true);
+        drq::conv_bwd_data(k.bwd[1], dr, p + k.cw[k1], k.c[b], dc, dn, B, st);
         std::swap(dc, dn);
       }
       drq::maxpool_bwd(dc, k.arg, dn, B, k.hin, k.hin, k.co, st);  // dn: grad wrt conv0's output
       const float* xin = s == 0 ? stk[0].xin_own : stk[s - 1].c[2];
-      drq::conv_wgrad(xin, dn, wparts[s][0], g + k.cw[0], g + k.cb[0], B, k.hin, k.hin, k.ci, k.co, false, st, true);
-      if (s > 0) drq::conv_bwd_data(dn, p + k.cw[0], nullptr, nullptr, dc, B, k.hin, k.hin, k.ci, k.co, st);
+      drq::conv_wgrad(k.wg[0], xin, dn, wparts[s][0], g + k.cw[0], g + k.cb[0], false, st, true);
+      if (s > 0) drq::conv_bwd_data(k.bwd[0], dn, p + k.cw[0], nullptr, nullptr, dc, B, st);
     }
     // every conv's weight / bias gradient from its partials, one launch (the segment table)
     drq::sum_parts_multi(d_segs, 15, seg_blocks, st);
@@ -463,6 +465,12 @@ int drq_create(const drq_config* c, int device, drq_engine** out) {
     if (!drq::conv_supported(k.ci, k.co) || !drq::conv_supported(k.co, k.co)) {
       delete e;
       return fail(-95, "conv channel counts not instantiated (scale 1, in_ch 4)");
+    }
+    for (int j = 0; j < 2; ++j) {  // the switches are read here, once per engine
+      const int hh = j == 0 ? k.hin : k.ho, cin = j == 0 ? k.ci : k.co;
+      k.fwd[j] = drq::conv_plan(0, B, hh, hh, cin, k.co);
+      k.bwd[j] = drq::conv_plan(1, B, hh, hh, cin, k.co);
+      k.wg[j] = drq::conv_plan(2, B, hh, hh, cin, k.co);
     }
     for (int q = 0; q < 5; ++q) {
       const int cin = q == 0 ? k.ci : k.co;
@@ -565,14 +573,13 @@ int drq_create(const drq_config* c, int device, drq_engine** out) {
   for (float** q : {&e->hc_on, &e->hc_tg, &e->dhc})
     if ((rc = e->alloc(q, (long long)B * NC))) return bad(rc);
   if ((rc = e->alloc(&e->m, (long long)B * Z))) return bad(rc);
-  {  // per-conv partial regions and the segment table of the one partial-sum launch
+  {  // per-conv partial regions and the segment table of the one partial-sum launch, from the plans
     std::vector<drq::SumSeg> segs;
     long long total = 0;
     for (int s = 0; s < 3; ++s)
       for (int j = 0; j < 5; ++j) {
-        const Stack& k = e->stk[s];
-        const int hh = j == 0 ? k.hin : k.ho, ci = j == 0 ? k.ci : k.co;
-        total += (long long)drq::conv_wgrad_blocks(B, hh, hh, ci, k.co) * (9LL * ci * k.co + k.co);
+        const drq::ConvPlan& pl = e->stk[s].wg[j != 0];
+        total += (long long)pl.rows * (9LL * pl.ci * pl.co + pl.co);
       }
     float* all = nullptr;
     if ((rc = e->alloc(&all, total))) return bad(rc);
@@ -580,8 +587,7 @@ int drq_create(const drq_config* c, int device, drq_engine** out) {
     for (int s = 0; s < 3; ++s)
       for (int j = 0; j < 5; ++j) {
         const Stack& k = e->stk[s];
-        const int hh = j == 0 ? k.hin : k.ho, ci = j == 0 ? k.ci : k.co;
-        const int G = drq::conv_wgrad_blocks(B, hh, hh, ci, k.co), n = 9 * ci * k.co + k.co;
+        const int ci = k.wg[j != 0].ci, G = k.wg[j != 0].rows, n = 9 * ci * k.co + k.co;
         e->wparts[s][j] = all;
         segs.push_back({all, e->g + k.cw[j], e->g + k.cb[j], G, n, 9 * ci * k.co, blk});
         blk += drq::sum_parts_blocks(ci, k.co);

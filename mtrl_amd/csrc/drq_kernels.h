@@ -30,50 +30,60 @@ void atari_sample_rows(const unsigned char* store, const unsigned char* nstore, 
 void aug_draw(unsigned long long seed, unsigned long long ctr, int B, int pad, int* crop_o, float* noise_o,
               int* crop_n, float* noise_n, hipStream_t st);
 bool conv_supported(int ci, int co);
-extern int g_drq_fwd_g, g_drq_bwd_g;  // conv channel groups per lane, 0: the engine's choice (experiments)
-extern int g_drq_mfma;  // f32-MFMA convs (experiment): bit 1 forward, 2 data grad, 4 weight grad (default 0)
-// the pre-round-6 conv kernels (one lane per pixel; im2col weight grad) instead of the row-tile
-// ones: bit 1 forward, 2 data grad, 4 weight grad; bit 8: the row-tile kernels at every shape (past
-// the measured per-shape choice) where bits 1-4 are clear; bit 16: no split2h MFMA convs; bit 32: the
-// split2h MFMA convs at every shape they support (default 0; tests and A/B)
-extern int g_drq_legacy;
-extern int g_drq_wg_blocks;  // the row-tile weight grad's grid cap (experiments; set before an engine exists)
-double conv_bench(int kind, int B, int H, int W, int ci, int co, int iters);
-// 3x3 / stride 1 / SAME on NHWC, kernel [3][3][ci][co]; relu_in applies ReLU to the input, res
-// (nullable) is added to the output.  w2 / bias2 (nullable): images [B1, B) use that second
-// parameter set (one launch over the online and the target passes)
-void conv_fwd(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
-              int ci, int co, bool relu_in, hipStream_t st, const float* w2 = nullptr, const float* bias2 = nullptr,
-              int B1 = -1);
-// din = conv^T(dout) * [mask > 0] (mask nullable) + dres (nullable)
-void conv_bwd_data(const float* dout, const float* w, const float* mask, const float* dres, float* din, int B, int H,
-                   int W, int ci, int co, hipStream_t st);
-// the row-tile weight-gradient kernel's geometry: tiles of R image rows (tiles = B ceil(H / R)), LDS
-// row stride SR floats, magic = ceil(2^32 / W) (q / W = umulhi(q, magic) for the q < R W it divides)
-struct WgGeo {
-  int H, W, R, SR, tiles;
-  unsigned magic;
+// The conv selection's switches (tests, experiments and A/B runs; include/mtsac_debug.h).  conv_plan
+// is their only reader: they act when an engine is created and when a debug conv entry point is
+// called, never on a plan that exists.
+struct ConvSwitches {
+  int fwd_g, bwd_g;  // pixel kernels' channels per lane, forward / data grad (0: the plan's choice)
+  // the pre-round-6 conv kernels (one lane per pixel; im2col weight grad) instead of the row-tile
+  // ones: bit 1 forward, 2 data grad, 4 weight grad; bit 8: the row-tile kernels at every shape (past
+  // the measured per-shape choice) where bits 1-4 are clear; bit 16: no split2h MFMA convs; bit 32: the
+  // split2h MFMA convs at every shape they support (default: MTSAC_DRQ_LEGACY in the environment, or 0)
+  int legacy;
+  int wg_blocks;  // > 0: the row-tile weight grad's grid cap
 };
-int conv_wgrad_blocks(int B, int H, int W, int ci, int co);
+ConvSwitches& conv_switches();
 // the row-tile forward / data-gradient kernels' geometry: n tiles of R rows per image, LDS row
 // stride SR floats, magic = ceil(2^32 / W), magic2 = ceil(2^32 / (W + 2))
 struct ConvGeo {
   int H, W, R, SR, n;
   unsigned magic, magic2;
 };
-// dw [3][3][ci][co], db [co] of a conv whose input is act(in); part: conv_wgrad_blocks(...) x
-// (9 ci co + co) floats
-// defer_sum: leave the partials for one sum_parts_multi launch over every conv of the backward
-void conv_wgrad(const float* in, const float* dout, float* part, float* dw, float* db, int B, int H, int W, int ci,
-                int co, bool relu_in, hipStream_t st, bool defer_sum = false);
-// what a conv launcher runs under the current masks (kind 0 forward, 1 data grad, 2 weight grad;
-// the launchers decide through the same functions): family 0 one lane per pixel / im2col, 1 row
-// tiles, 2 split2h MFMA, 3 f32 MFMA; R rows per tile and n tiles per image (0 when not tiled);
-// grid blocks
-struct ConvPath {
-  int family, R, n, blocks;
+// the row-tile weight-gradient kernel's geometry: tiles of R image rows (tiles = B ceil(H / R)), LDS
+// row stride SR floats, magic = ceil(2^32 / W) (q / W = umulhi(q, magic) for the q < R W it divides)
+struct WgGeo {
+  int H, W, R, SR, tiles;
+  unsigned magic;
 };
-ConvPath conv_path(int kind, int B, int H, int W, int ci, int co);
+// What runs for one 3x3 / stride 1 / SAME conv on NHWC images [H][W], kernel [3][3][ci][co]: kind 0
+// forward, 1 data gradient, 2 weight gradient.  family 0: one lane per pixel (G channels per lane) /
+// im2col; 1: row tiles (ng channel groups per pixel); 2: split2h MFMA.  geo: the tiled forward /
+// data-grad families; wg: the row-tile weight grad.  A forward / data-grad plan holds for any batch
+// (the launch takes it); a weight-grad plan is for batch B alone and writes `rows` partial rows of
+// 9 ci co + co floats, which is what its caller allocates.
+struct ConvPlan {
+  int kind, H, W, ci, co;
+  int family, ng, G;
+  ConvGeo geo;
+  WgGeo wg;
+  int B, rows;
+};
+ConvPlan conv_plan(int kind, int B, int H, int W, int ci, int co);
+// grid blocks of the plan's launch over B images (the weight grad: its partial rows)
+int conv_blocks(const ConvPlan& pl, int B);
+double conv_bench(int kind, int B, int H, int W, int ci, int co, int iters);
+// relu_in applies ReLU to the input, res (nullable) is added to the output.  w2 / bias2 (nullable):
+// images [B1, B) use that second parameter set (one launch over the online and the target passes)
+void conv_fwd(const ConvPlan& pl, const float* in, const float* w, const float* bias, const float* res, float* out,
+              int B, bool relu_in, hipStream_t st, const float* w2 = nullptr, const float* bias2 = nullptr,
+              int B1 = -1);
+// din = conv^T(dout) * [mask > 0] (mask nullable) + dres (nullable)
+void conv_bwd_data(const ConvPlan& pl, const float* dout, const float* w, const float* mask, const float* dres,
+                   float* din, int B, hipStream_t st);
+// dw [3][3][ci][co], db [co] of a conv whose input is act(in); part: pl.rows x (9 ci co + co) floats
+// defer_sum: leave the partials for one sum_parts_multi launch over every conv of the backward
+void conv_wgrad(const ConvPlan& pl, const float* in, const float* dout, float* part, float* dw, float* db,
+                bool relu_in, hipStream_t st, bool defer_sum = false);
 // one conv's partial sums: part[G][n] -> dw[0, nw), db[0, n - nw); blocks [blk0, blk0 + sum_parts_blocks)
 struct SumSeg {
   const float* part;

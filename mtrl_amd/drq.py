@@ -101,8 +101,8 @@ def _f32(a):
 
 
 def debug_conv_path(kind: int, B: int, H: int, W: int, ci: int, co: int) -> tuple:
-    """(family, rows per tile, tiles per image, grid blocks) of the conv launcher under the current
-    masks: family 0 one lane per pixel / im2col, 1 row tiles, 2 split2h MFMA, 3 f32 MFMA."""
+    """(family, rows per tile, tiles per image, grid blocks) of the conv's plan under the current
+    switches: family 0 one lane per pixel / im2col, 1 row tiles, 2 split2h MFMA."""
     out = np.zeros(4, np.int32)
     _dbg_check(L.load().mtsac_debug_drq_conv_path(kind, B, H, W, ci, co, _ptr(out)))
     return tuple(int(v) for v in out)

@@ -52,19 +52,17 @@ def _lib():
 
 
 @contextlib.contextmanager
-def _masks(legacy=0, mfma=0, groups=(0, 0), wg_blocks=0):
+def _masks(legacy=0, groups=(0, 0), wg_blocks=0):
     lib = _lib()
-    old = (lib.mtsac_debug_drq_legacy(-1), lib.mtsac_debug_drq_mfma(-1), lib.mtsac_debug_drq_wgrad_blocks(-1))
+    old = (lib.mtsac_debug_drq_legacy(-1), lib.mtsac_debug_drq_wgrad_blocks(-1))
     old_g = lib.mtsac_debug_drq_groups(*groups)
     try:
         lib.mtsac_debug_drq_legacy(legacy)
-        lib.mtsac_debug_drq_mfma(mfma)
         lib.mtsac_debug_drq_wgrad_blocks(wg_blocks)
         yield
     finally:
         lib.mtsac_debug_drq_legacy(old[0])
-        lib.mtsac_debug_drq_mfma(old[1])
-        lib.mtsac_debug_drq_wgrad_blocks(old[2])
+        lib.mtsac_debug_drq_wgrad_blocks(old[1])
         lib.mtsac_debug_drq_groups(old_g & 255, old_g >> 8)
 
 
@@ -151,7 +149,6 @@ FORCE = {
     "pixel_g8": (0, {0: dict(legacy=1 | 16, groups=(8, 8)), 1: dict(legacy=2 | 16, groups=(8, 8))}),
     "rows": (1, {0: dict(legacy=16), 1: dict(legacy=16 | 8), 2: dict(legacy=16 | 8)}),
     "split2h": (2, {0: dict(legacy=32), 1: dict(legacy=32)}),
-    "mfma": (3, {0: dict(mfma=1), 1: dict(mfma=2), 2: dict(mfma=4)}),
 }
 CASES = [(k, f) for f, (_, by_kind) in FORCE.items() for k in by_kind]
 
@@ -220,7 +217,7 @@ def test_default_selection_flips_where_documented():
             assert _path(1, (2, 15, 16), pair)[0] == (1 if pair[1] == 16 else 0), pair
 
 
-@pytest.mark.parametrize("force", ["pixel", "rows", "split2h", "mfma", "default"])
+@pytest.mark.parametrize("force", ["pixel", "rows", "split2h", "default"])
 def test_conv_forward_two_parameter_sets(force):
     """Images [B1, B) on the second parameter set, B1 = 0..B; B1 H W a multiple of 256 and not."""
     from mtrl_amd.drq import debug_conv_fwd
